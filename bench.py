@@ -9,22 +9,24 @@ decomposed, paths + transcripts materialised in host memory.  The stages are pip
 objects, as a caller feeding a stream of batches would run them: when the timed region starts the batches of the first steps are
 already resident in HBM (staged during the warm-up) and the staging of later ones runs under the kernels.  At N > 1 the step also
 holds the RCCL gather of the finished transcripts to rank 0, the path's only exchange step.
-`value` is that rate.  `value_resident` is the rate of a second loop over inputs that stay resident in HBM (kernels + D2H + decode
-only, nothing staged inside the window); kernels never overlap each other, so the per-launch HIP-event time is that of one kernel,
-and `roofline` is computed from the launches of the resident loop.
+`value` is that rate.  `value_resident` (--full, or the headline itself with --skip-h2d-loop) is the rate of a second loop over inputs
+that stay resident in HBM (kernels + D2H + decode only, nothing staged inside the window); kernels never overlap each other, so the
+per-launch HIP-event time is that of one kernel, and `roofline` is computed from the launches of the resident loop.
 
 Workload (N=1): BASELINE.json configs[1] -- 100k synthetic splice graphs, 64 vertices / 256 edges each.
 N > 1: bundles shard embarrassingly; every rank decomposes its own 100k-graph shard (weak scaling, seed 1004+rank).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--graphs G]
-        (--gpus N > 1 without a launcher's WORLD_SIZE in the environment: this process starts the N ranks itself, as
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--graphs G] [--full] [--dump-outputs DIR]
+        (a plain run times the headline loop only; --full adds the resident loop with its roofline, the secondary shapes and the
+         CPU baselines; --dump-outputs DIR writes the last timed step's results as DIR/<name>.npy;
+         --gpus N > 1 without a launcher's WORLD_SIZE in the environment: this process starts the N ranks itself, as
          `python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py ...`, before it touches the GPU,
          relays rank 0's JSON line and exits with the launcher's code)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
 Prints ONE JSON line on rank 0.  `roofline.achieved` = algorithmic bytes per launch (packed input + packed path
-records) / mean kernel duration measured with HIP events on the launch stream over the timed region.  `cpu_baseline` = the oracle
-(CPU restatement of the reference, oracle/) on a bounded sample of the same workload on the host cores, 1 thread and all cores.
+records) / mean kernel duration measured with HIP events on the launch stream over the timed region.  `cpu_baseline` (--full) = the
+oracle (CPU restatement of the reference, oracle/) on a bounded sample of the same workload on the host cores, 1 thread and all cores.
 """
 from __future__ import annotations
 
@@ -67,6 +69,8 @@ def parse_args(argv=None):
     ap.add_argument("--no-secondary", action="store_true", help="skip the cfg3 / flow-weight kernel timings (the `secondary` block)")
     ap.add_argument("--backend", choices=("nccl", "gloo"), default="nccl", help="gloo: CPU rehearsal of the multi-rank plumbing (needs --dry-run)")
     ap.add_argument("--dry-run", action="store_true", help="no GPU work: every rank stages its shard and enters the exchange with an empty stream (CPU tier)")
+    ap.add_argument("--full", action="store_true", help="measure everything beyond the headline too: the resident-input loop (value_resident, download_ms, roofline), the secondary shapes and the CPU baselines; a plain run times the headline steps only")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write what the last timed step computed (rank 0's batch) as DIR/<name>.npy, float64")
     return ap.parse_args(argv)
 
 
@@ -333,6 +337,41 @@ def dispatcher_rate(submitters=8):
         return {"skipped": f"{type(e).__name__}: {e}"}
 
 
+def dump_outputs(out_dir, batch, n_sample=4096, seed=0, max_bytes=64 << 20):
+    """--dump-outputs: what the last timed step handed its caller -- the host path table and the exon-joined transcripts of every
+    graph -- as float64 .npy files, so that two builds can be compared output for output.  Per-graph arrays cover every graph (up to
+    1M graphs); per-path arrays cover the paths of a fixed, seeded sample of `n_sample` graphs (the whole table of the 100k-graph
+    workload would be about 200 MB).  Ragged arrays are flattened, their lengths stored beside them."""
+    import numpy as np
+    r = batch.result()
+    cov, eo, exons = batch.transcripts()
+    n = len(r.status)
+    po = r.path_offset.astype(np.int64)
+
+    def ragged(off, idx):                                # positions of the rows of every entry idx[i] of a CSR offset array, in order
+        lens = off[idx + 1] - off[idx]
+        return np.repeat(off[idx] - (np.cumsum(lens) - lens), lens) + np.arange(int(lens.sum()), dtype=np.int64), lens
+
+    g = np.sort(np.random.default_rng(seed).choice(n, size=min(n, n_sample), replace=False))
+    p, paths_per_sampled = ragged(po, g)
+    pv, n_vertices = ragged(r.pv_offset.astype(np.int64), p)
+    ex, n_exons = ragged(eo, p)
+    every = np.arange(n) if n <= (1 << 20) else g
+    out = {"status": r.status[every], "paths_per_graph": np.diff(po)[every],
+           "path_weight_sum": np.bincount(np.repeat(np.arange(n), np.diff(po)), weights=r.weight, minlength=n)[every],
+           "sample_graph": g, "sample_paths_per_graph": paths_per_sampled,
+           "path_weight": r.weight[p], "path_abd": r.abd[p], "path_conf": r.conf[p], "path_reads": r.reads[p],
+           "path_length": r.length[p], "path_count": r.count[p], "path_strand": r.strand[p], "path_coverage": cov[p],
+           "path_n_vertices": n_vertices, "path_vertices": r.path_vertices[pv], "path_n_exons": n_exons, "path_exons": exons[ex]}
+    out = {k: np.ascontiguousarray(v, dtype=np.float64) for k, v in out.items()}
+    total = sum(v.nbytes for v in out.values())
+    if total > max_bytes:
+        raise RuntimeError(f"--dump-outputs: {total} bytes exceed the {max_bytes}-byte budget")
+    os.makedirs(out_dir, exist_ok=True)
+    for k, v in out.items():
+        np.save(os.path.join(out_dir, k + ".npy"), v)
+
+
 def main() -> int:
     args = parse_args()
     world_env = os.environ.get("WORLD_SIZE")
@@ -429,6 +468,8 @@ def main() -> int:
         if dist_on:
             dist.barrier()
         return time.perf_counter()
+
+    last = [None]                                        # the batch of the last step run_steps timed (its results stay on the host)
 
     def run_steps(w, k, staged, raw=False, prime=False):
         """w untimed + k timed passes through ONE pipeline.  staged=True: host arrays in -> host results out, three stages on three
@@ -543,7 +584,7 @@ def main() -> int:
                 finish(prev); release(prev); prev = None
                 drained()
                 t0 = bracket(); stage_s[2] = 0.0; stage_s[3] = 0.0; main_s = [0.0, 0.0, 0.0]
-        ms.append(finish(prev)); release(prev)
+        ms.append(finish(prev)); last[0] = prev; release(prev)
         drained()
         t1 = bracket()
         xq.put(None)
@@ -565,32 +606,38 @@ def main() -> int:
     # one plain pass per batch object first (untimed, in front of the W warm-up steps): every pinned / device buffer exists, every batch is resident
     for b in batches:
         b.clear(); b.add(pg); b.upload(); b.run(); b.download()
+    # the headline loop: host arrays in -> host results out, or with --skip-h2d-loop the resident loop below
     if args.skip_h2d_loop:
         elapsed_h2d, kms_h2d = None, [float("nan")]
     else:
         elapsed_h2d, kms_h2d = run_steps(args.warmup, args.steps, True, prime=True)   # host arrays in -> host results out (also: one pass per batch object, so every pinned / device buffer exists and every batch is resident)
-    for k_ in dl_acc:
-        dl_acc[k_] = 0
-    elapsed, kms = run_steps(args.warmup, args.steps, False)           # THE timed region: W untimed + K timed steps over inputs resident in HBM
-    dl = {k_: (dl_acc[k_] / max(1, dl_acc["n"])) for k_ in ("wait_kernel", "status_retries", "copy", "decode", "bytes_to_host")}
+        if args.dump_outputs and rank == 0:
+            dump_outputs(args.dump_outputs, last[0])
+    resident = args.full or elapsed_h2d is None          # the resident loop runs in a --full run and as the headline of a profiling run
+    if resident:
+        for k_ in dl_acc:
+            dl_acc[k_] = 0
+        elapsed, kms = run_steps(args.warmup, args.steps, False)       # W untimed + K timed steps over inputs resident in HBM
+        dl = {k_: (dl_acc[k_] / max(1, dl_acc["n"])) for k_ in ("wait_kernel", "status_retries", "copy", "decode", "bytes_to_host")}
+        if elapsed_h2d is None and args.dump_outputs and rank == 0:
+            dump_outputs(args.dump_outputs, last[0])
 
-    batch = batches[0]
+    batch = last[0]                                      # every batch holds the same graphs; the ones staged beyond the window hold no results
     res = batch.result()
     n_bad = int((res.status != 0).sum())
-    in_b, out_b = batch.algorithmic_bytes()
-    k_ms = float(np.mean(kms))
     info = batch.class_info(1)
-    iters = int(batch.iterations().astype(np.int64).sum())
-    pmc = committed_pmc(args)
-    traffic = pmc.get("traffic_bytes_per_launch")
+    if resident:
+        in_b, out_b = batch.algorithmic_bytes()
+        k_ms = float(np.mean(kms))
+        iters = int(batch.iterations().astype(np.int64).sum())
+        pmc = committed_pmc(args)
+        traffic = pmc.get("traffic_bytes_per_launch")
 
     if rank == 0:
-        value_resident = args.graphs * world * args.steps / elapsed
         # the metric is H2D + kernel + D2H inclusive.  (A profiling run with --skip-h2d-loop has no such loop: it reports
         # the resident-input rate and says so in `value_is`.)
         el_value = elapsed_h2d if elapsed_h2d else elapsed
         value = args.graphs * world * args.steps / el_value
-        achieved = (in_b + out_b) / (k_ms / 1e3) / 1e9
         step_text = ("decomposition kernels (exon join of every path into its record + result index written by the kernel) + D2H of status / records (paths and transcripts) / index + decode into the host path table with coverage = log(1 + weight)"
                      + (" + RCCL gather of the finished transcripts to rank 0 (device stream -> xGMI -> HBM of rank 0; rank 0's merge of the gathered streams into one transcript_set is NOT inside the step: it is host work at ~2.3 M bundles/s, profiles/r04/m_funnel_rehearsal_w8.txt)" if dist_on else "") + "; kernel k+1 is launched before the results of batch k are downloaded, so copies and decode run under the next kernel")
         line = {
@@ -599,27 +646,31 @@ def main() -> int:
             "dtype": "f64", "data": "synthetic", "source": source_stamp(),
             "value_is": "h2d_inclusive" if elapsed_h2d else "resident (--skip-h2d-loop: profiling run)",
             "timed_step": ("H2D + kernel + D2H inclusive (SURVEY.md 8d): ald_batch_add_packed into the pinned host arrays of the batch + H2D of every array, three-stage pipeline on three host threads over 4 rotating batch objects -- K kernels, K downloads and K stagings between the brackets; the batches of the first timed steps are resident in HBM when the window opens (staged during the warm-up), later ones are staged under the kernels; " if elapsed_h2d else "inputs resident in HBM; ") + step_text,
-            "value_resident": value_resident, "ms_per_step_resident": elapsed / args.steps * 1e3,
-            "resident_step": "the same step over inputs that stay resident in HBM (nothing staged inside the window): " + step_text,
-            "download_ms": {"wait_for_kernel": dl["wait_kernel"], "status_and_retries": dl["status_retries"], "d2h_copies": dl["copy"], "decode_paths_and_transcripts": dl["decode"],
-                            "bytes_to_host_per_step": dl["bytes_to_host"]},
-            "config": {"workload": f"{args.graphs} synthetic splice graphs per GPU, {args.vertices} vertices / {args.edges} edges each "
-                                   + ("(BASELINE.json configs[1]; U[1,100) FP64 weights, 1 supporting sample per edge, no phasing paths)" if args.weights == "uniform" else
-                                      f"(BASELINE.json configs[1] shape with {args.weights} weights -- secondary distribution, not the headline)"),
-                       "graphs_per_gpu": args.graphs, "sharding": "independent graphs per rank, RCCL gather of finished transcripts to rank 0" if world > 1 else "single GPU",
-                       "failed_graphs": n_bad, "paths_per_graph": float(len(res.weight)) / max(1, args.graphs),
-                       "workgroups_per_cu": info["blocks_per_cu"], "grid": info["blocks_last_run"]},
-            "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
-                         "traffic": traffic, "traffic_source": pmc.get("source"),
-                         "traffic_gbs": (traffic / (k_ms / 1e3) / 1e9) if traffic else None,      # measured HBM traffic over this run's kernel time
-                         "kernel": "ald_decomp_kernel_c1", "kernel_ms": k_ms, "kernel_ms_min": float(np.min(kms)), "kernel_ms_median": float(np.median(kms)), "kernel_ms_h2d_loop": float(np.mean(kms_h2d)),
-                         "algorithmic_bytes_per_launch": in_b + out_b, "bytes_per_graph": (in_b + out_b) / args.graphs,
-                         "kernel_graphs_per_s": args.graphs / (k_ms / 1e3),
-                         # what actually bounds this kernel (dependent mutate-and-rescan steps, not bytes)
-                         "steps_per_graph": iters / max(1, args.graphs), "steps_per_s_per_cu": iters / (k_ms / 1e3) / N_CUS,
-                         "instr_per_graph": pmc.get("instr_per_graph"), "lds_bytes_per_workgroup": pmc.get("lds_bytes_per_workgroup")},
         }
-        if world == 1 and not args.no_secondary:
+        if resident:
+            line.update({
+                "value_resident": args.graphs * world * args.steps / elapsed, "ms_per_step_resident": elapsed / args.steps * 1e3,
+                "resident_step": "the same step over inputs that stay resident in HBM (nothing staged inside the window): " + step_text,
+                "download_ms": {"wait_for_kernel": dl["wait_kernel"], "status_and_retries": dl["status_retries"], "d2h_copies": dl["copy"], "decode_paths_and_transcripts": dl["decode"],
+                                "bytes_to_host_per_step": dl["bytes_to_host"]}})
+        line["config"] = {"workload": f"{args.graphs} synthetic splice graphs per GPU, {args.vertices} vertices / {args.edges} edges each "
+                           + ("(BASELINE.json configs[1]; U[1,100) FP64 weights, 1 supporting sample per edge, no phasing paths)" if args.weights == "uniform" else
+                              f"(BASELINE.json configs[1] shape with {args.weights} weights -- secondary distribution, not the headline)"),
+               "graphs_per_gpu": args.graphs, "sharding": "independent graphs per rank, RCCL gather of finished transcripts to rank 0" if world > 1 else "single GPU",
+               "failed_graphs": n_bad, "paths_per_graph": float(len(res.weight)) / max(1, args.graphs),
+               "workgroups_per_cu": info["blocks_per_cu"], "grid": info["blocks_last_run"]}
+        if resident:
+            achieved = (in_b + out_b) / (k_ms / 1e3) / 1e9
+            line["roofline"] = {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
+                                "traffic": traffic, "traffic_source": pmc.get("source"),
+                                "traffic_gbs": (traffic / (k_ms / 1e3) / 1e9) if traffic else None,      # measured HBM traffic over this run's kernel time
+                                "kernel": "ald_decomp_kernel_c1", "kernel_ms": k_ms, "kernel_ms_min": float(np.min(kms)), "kernel_ms_median": float(np.median(kms)), "kernel_ms_h2d_loop": float(np.mean(kms_h2d)),
+                                "algorithmic_bytes_per_launch": in_b + out_b, "bytes_per_graph": (in_b + out_b) / args.graphs,
+                                "kernel_graphs_per_s": args.graphs / (k_ms / 1e3),
+                                # what actually bounds this kernel (dependent mutate-and-rescan steps, not bytes)
+                                "steps_per_graph": iters / max(1, args.graphs), "steps_per_s_per_cu": iters / (k_ms / 1e3) / N_CUS,
+                                "instr_per_graph": pmc.get("instr_per_graph"), "lds_bytes_per_workgroup": pmc.get("lds_bytes_per_workgroup")}
+        if args.full and world == 1 and not args.no_secondary:
             # the other single-GPU shapes of BASELINE.json / SURVEY.md 8d, kernel time only (parity for them: tests/test_gpu_parity.py)
             sec = {}
             cfg3 = A.synth(seed=1003, n_graphs=10000, v_min=8, v_max=512, edges_per_vertex=4)
@@ -649,7 +700,7 @@ def main() -> int:
             sec["end_to_end_with_sink"] = sink_pipeline(A, pg, args.graphs)
             sec["dispatcher"] = dispatcher_rate()
             line["secondary"] = sec
-        if args.cpu_sample > 0 and world == 1:           # reported at N = 1 only
+        if args.full and args.cpu_sample > 0 and world == 1:           # reported at N = 1 only
             line["cpu_baseline"], line["cpu_baseline_1t"] = cpu_baseline_legs(pg, args.cpu_sample)
         emit(line)
     for b in batches:

@@ -19,8 +19,12 @@
                       write_features(ostream), write_features(int) (gtf/transcript.cc:318-494, oracle/_ref/ref_gtf)
                       -> pins ald_gtf_format_transcript / ald_gtf_format_features
 
+  ref_live.json       the cases the "live" pins generate (router: make_golden.router_case from seed 99; tset: tset_case from
+                      seed 77) with the answers of oracle/_ref/ref_router / ref_tset, so that those pins run where the
+                      reference-built drivers do not exist (tests/test_oracle_pins.py, tests/test_tset_cpu.py)
+
 Needs /root/reference (for the _ref binaries); run from the repo root:  python tests/golden/make_golden.py
-(`python tests/golden/make_golden.py gtf` / `router` regenerate ref_gtf.json / ref_router.json only)
+(`python tests/golden/make_golden.py gtf` / `router` / `live` regenerate ref_gtf.json / ref_router.json / ref_live.json only)
 """
 import json
 import os
@@ -211,8 +215,41 @@ def make_router(n_cases=240):
     return len(cases)
 
 
+def live_router_cases(exe, n_cases=150, seed=99):
+    """the one-vertex cases of the live router pin and the reference's answers: cases on which the reference aborts are dropped"""
+    rng = random.Random(seed)
+    cases = []
+    while len(cases) < n_cases:
+        sc = router_case(rng)
+        r = subprocess.run([exe], input=sc, capture_output=True, text=True)
+        if r.returncode != 0:
+            continue
+        cases.append({"script": sc, "out": "".join(ln + "\n" for ln in r.stdout.splitlines() if ln.startswith("@"))})
+    return cases
+
+
+def live_tset_cases(exe, seed=77):
+    """the transcript groups of the live sink pin and the merged set the reference makes of them"""
+    rng = random.Random(seed)
+    cases = []
+    for ng, ns, nc in ((25, 2, 5), (200, 6, 30)):
+        groups = tset_case(rng, ng, ns, nc)
+        out = subprocess.run([exe], input=tset_text(groups), capture_output=True, text=True, check=True).stdout
+        cases.append({"groups": groups, "items": tset_parse(out)})
+    return cases
+
+
+def make_live():
+    d = {"router": live_router_cases(os.path.join(ROOT, "oracle/_ref/ref_router")), "tset": live_tset_cases(os.path.join(ROOT, "oracle/_ref/ref_tset"))}
+    json.dump(d, open(os.path.join(HERE, "ref_live.json"), "w"), indent=0)
+    return len(d["router"]), len(d["tset"])
+
+
 def main():
     subprocess.run(["make", "-C", os.path.join(ROOT, "oracle")], check=True, stdout=subprocess.DEVNULL)
+    if len(sys.argv) > 1 and sys.argv[1] == "live":
+        print("ref_live.json: %d router cases, %d tset cases" % make_live())
+        return
     if len(sys.argv) > 1 and sys.argv[1] == "gtf":
         print("ref_gtf.json:", make_gtf(), "transcripts")
         return
@@ -251,6 +288,7 @@ def main():
     json.dump(tcases, open(os.path.join(HERE, "ref_tset.json"), "w"))
     make_gtf()
     make_router()
+    make_live()
     # ---- oracle regression fixture ----
     import aletsch_amd as A
     import common

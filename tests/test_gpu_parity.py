@@ -894,7 +894,7 @@ def test_row_form_of_the_kernels_on_gpu():
 
 
 def test_bench_line_and_its_exchange_path():
-    """bench.py in a fresh process, as the driver starts it: ONE JSON line carrying the contract's keys, `roofline` and `cpu_baseline`; and
+    """bench.py --full in a fresh process, as the driver starts it: ONE JSON line carrying the contract's keys, `roofline` and `cpu_baseline`; and
     once more with the multi-rank exchange forced on for the single rank this box has (ALD_BENCH_FORCE_DIST: process group over RCCL,
     transcript stream built on the device, gathered to rank 0, merged there) -- the path `--gpus N` takes on a multi-GPU node"""
     import json, os, subprocess, sys
@@ -902,7 +902,7 @@ def test_bench_line_and_its_exchange_path():
     for force in (False, True):
         e = dict(env, ALD_BENCH_FORCE_DIST="1") if force else env
         r = subprocess.run([sys.executable, os.path.join(common.ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--graphs", "20000", "--no-secondary",
-                            "--cpu-sample", "0" if force else "2000"], capture_output=True, text=True, timeout=280, env=e)
+                            "--cpu-sample", "0" if force else "2000", "--full"], capture_output=True, text=True, timeout=280, env=e)
         assert r.returncode == 0, r.stderr[-2000:]
         lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
         assert len(lines) == 1, r.stdout[-2000:]
@@ -913,3 +913,40 @@ def test_bench_line_and_its_exchange_path():
         assert j["roofline"]["bound"] == "hbm" and 0 < j["roofline"]["frac"] < 1 and j["config"]["failed_graphs"] == 0
         if not force:
             assert j["cpu_baseline"]["kind"] == "port" and j["cpu_baseline"]["value"] > 0
+
+
+def test_bench_plain_run_and_its_outputs(tmp_path):
+    """A plain bench.py run (no --full) times the headline loop only: the contract's keys, none of the figures that take runs of their
+    own.  --dump-outputs writes what the last timed step computed, float64 and within 64 MB, the same in two runs, and the sampled
+    graphs' path tables equal the oracle's decomposition of the same graphs."""
+    import json, subprocess, sys
+    from aletsch_amd.packed import DecompResult
+    dumps = []
+    for i in range(2):
+        d = tmp_path / str(i)
+        r = subprocess.run([sys.executable, os.path.join(common.ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--graphs", "20000",
+                            "--dump-outputs", str(d)], capture_output=True, text=True, timeout=280)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
+        assert len(lines) == 1, r.stdout[-2000:]
+        j = json.loads(lines[0])
+        for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "steps", "warmup", "config"):
+            assert k in j, k
+        assert j["metric"] == "bundles/sec" and j["value"] > 0 and j["steps"] == 2 and j["value_is"] == "h2d_inclusive" and j["config"]["failed_graphs"] == 0
+        assert not {"value_resident", "download_ms", "roofline", "secondary", "cpu_baseline", "cpu_baseline_1t"} & set(j), sorted(j)
+        out = {f[:-4]: np.load(d / f) for f in os.listdir(d)}
+        assert all(a.dtype == np.float64 for a in out.values()) and sum(a.nbytes for a in out.values()) <= 64 << 20
+        dumps.append(out)
+    a, b = dumps
+    assert sorted(a) == sorted(b) and all(np.array_equal(a[k], b[k]) for k in a)
+    assert len(a["status"]) == 20000 and (a["status"] == 0).all() and a["paths_per_graph"].sum() > 0
+    g = a["sample_graph"].astype(np.int64)
+    po = np.concatenate([[0], np.cumsum(a["sample_paths_per_graph"])]).astype(np.int32)
+    got = DecompResult(status=a["status"][g].astype(np.int32), path_offset=po, weight=a["path_weight"], abd=a["path_abd"], conf=a["path_conf"],
+                       reads=a["path_reads"], length=a["path_length"].astype(np.int32), count=a["path_count"].astype(np.int32),
+                       strand=a["path_strand"].astype(np.int8), pv_offset=np.concatenate([[0], np.cumsum(a["path_n_vertices"])]).astype(np.int64),
+                       path_vertices=a["path_vertices"].astype(np.int32))
+    pg = A.synth(seed=1002, n_graphs=20000, v_min=64, v_max=64, fixed_edges=256)         # bench.py's workload at N = 1
+    want = common.oracle_run(pg.select(g), threads=8)[0]
+    bad = common.compare_results(want, got, len(g), conf_tol=1e-9)
+    assert not bad, bad[:5]

@@ -6,7 +6,6 @@ The sink is host code behind the C ABI, so it runs in the CPU tier; every field 
 """
 import json
 import os
-import subprocess
 
 import pytest
 
@@ -68,18 +67,20 @@ def test_sink_merge_semantics_small():
     assert it[1]["coverage"] == 9.0 and it[1]["exons"] == [(1000, 1600)] and it[1]["cov2"] == 9.0
 
 
-@pytest.mark.skipif(not os.path.exists(os.path.join(os.path.dirname(HERE), "oracle", "_ref", "ref_tset")), reason="oracle/_ref/ref_tset not built")
 def test_sink_matches_live_reference_build():
-    import random
+    """two more cases of make_golden.tset_case (seed 77): the reference is asked again where build() could make oracle/_ref/ref_tset
+    (and must repeat the merged sets stored in tests/golden/ref_live.json); elsewhere the stored sets stand in"""
     import sys
     sys.path.insert(0, os.path.join(HERE, "golden"))
     import make_golden as mg
-    rng = random.Random(77)
-    for ng, ns, nc in ((25, 2, 5), (200, 6, 30)):
-        groups = mg.tset_case(rng, ng, ns, nc)
-        out = subprocess.run([os.path.join(os.path.dirname(HERE), "oracle", "_ref", "ref_tset")], input=mg.tset_text(groups), capture_output=True, text=True, check=True).stdout
-        s = A.TranscriptSink(0.8); s.add_groups(groups)
-        check(s.items(), mg.tset_parse(out))
+    cases = json.load(open(os.path.join(HERE, "golden", "ref_live.json")))["tset"]
+    exe = os.path.join(os.path.dirname(HERE), "oracle", "_ref", "ref_tset")
+    if os.path.exists(exe):
+        assert json.loads(json.dumps(mg.live_tset_cases(exe))) == cases
+    assert len(cases) == 2
+    for c in cases:
+        s = A.TranscriptSink(0.8); s.add_groups(as_groups(c))
+        check(s.items(), c["items"])
 
 
 def test_sink_containers_under_sanitizers():
