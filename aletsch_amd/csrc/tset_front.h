@@ -1,0 +1,61 @@
+// tset_front.h -- what the two transcript-set translation units share: the device front end of a batch's transcripts (tset_reduce.hip)
+// and the record / flat-set types both sides read.  tset_reduce.hip folds a batch into an EMPTY set (row f3); tset_resident.hip folds it
+// into a set that stays in HBM across calls.  Not installed, not part of the ABI.
+#pragma once
+#include "ald_internal.h"
+#include <string>
+#include <vector>
+
+#define HCHK(x) do { hipError_t e_ = (x); if(e_ != hipSuccess) return ald_set_err(ALD_ERR_HIP, std::string(#x) + ": " + hipGetErrorString(e_)); } while(0)
+
+enum { TX_BLOCK = 256 };
+static const uint64_t TX_HOST = ~0ull;                 // key of a transcript the host merges (fewer than two exons)
+inline unsigned grid_for(int64_t n) { return (unsigned)((n + TX_BLOCK - 1) / TX_BLOCK); }
+
+// The paths of a batch as the kernels see them: record offsets in (graph, path) order + the record pool.  A record carries the joined
+// exons of its transcript behind the vertex list (decomp_common.h), written by the decomposition kernel, so nothing here needs the
+// staged graphs or a host-side parse.
+struct TxIn { const unsigned long long *roff; const uint32_t *pool; int64_t np; };
+__host__ __device__ inline const int32_t *rec_exons(const uint32_t *r) { return (const int32_t*)(r + REC_HDR_WORDS + r[2]); }
+
+// first: path (in (graph, path) order) whose record the item takes its exons, strand and id from
+struct TxGroup { int64_t first; unsigned long long first_off; int32_t count, count1, lo, hi; double coverage, cov2, conf, abd; uint32_t bucket; int32_t nw, graph, path, strand, pad; };
+// one (group, sample) run: the per-sample maxima of a group's members from one sample
+struct TxSample { int32_t gid, sid, count1, pad; double cov2, conf, abd; };
+
+// scratch of a front end run (owned by a batch or a resident set and kept across calls, or temporary for the stream entry point)
+struct RedScratch { DevBuf *red; PinBuf *pin; hipStream_t st; };
+
+// What the front end leaves behind.  In S.red: [2] coverage per path, [6] sorted group keys, [7] sorted (group, sample) keys,
+// [8] path of every sorted position (sidx), [11] head flags, [12] 1-based group id of every sorted position, [13] TxGroup[n_groups],
+// [17] TxSample[n_runs] (sorted by group, then sample id).  host_paths: the transcripts with fewer than two exons, (graph, path) order.
+// ev0 (optional): recorded once the inputs are on the device, i.e. where the device time of the caller's section begins.
+struct TxFront { int64_t np = 0, n_dev = 0; int32_t n_groups = 0, n_runs = 0; std::vector<int64_t> host_paths; hipEvent_t ev0 = nullptr; bool sid_on_device = false; };
+inline const uint64_t *tx_skey(const RedScratch &S) { return (const uint64_t*)S.red[6].p; }
+inline const int64_t *tx_sidx(const RedScratch &S) { return (const int64_t*)S.red[8].p; }
+inline const int32_t *tx_head(const RedScratch &S) { return (const int32_t*)S.red[11].p; }
+inline const int32_t *tx_gid(const RedScratch &S) { return (const int32_t*)S.red[12].p; }
+inline TxGroup *tx_groups(const RedScratch &S) { return (TxGroup*)S.red[13].p; }
+inline TxSample *tx_samples(const RedScratch &S) { return (TxSample*)S.red[17].p; }
+
+// exon join / bucket hash / stable sort by group / head flags / group ids: F.n_dev, F.n_groups, F.host_paths.  h_cov: coverage per path
+// (host libm), sid: sample per graph or null.  Enqueued on S.st; returns after the counts are on the host.
+int tx_front_groups(RedScratch S, TxIn in, const double *h_cov, int n_graphs, const int32_t *sid, TxFront &F);
+// the fold of every group (tx_fold) and its per-sample runs (tx_sfold).  start_idx[group] >= 0: the group lands on a resident item whose
+// coverage start_cov[start_idx[group]] the group's graphs add to, one by one ((c + s1) + s2) + ...; null: every group starts empty.
+int tx_front_fold(RedScratch S, TxIn in, TxFront &F, const int64_t *start_idx, const double *start_cov);
+// the transcripts with fewer than two exons into `into`, graph by graph (one per-graph set per graph, assembler.cc:1105-1133)
+void tx_host_singles(aletsch::transcript_sink &into, const std::vector<int64_t> &host_paths, const uint32_t *h_pool, const unsigned long long *h_roff,
+                     const double *h_cov, const int64_t *h_tid, const int32_t *sid, const int64_t *label, int64_t tid_base);
+// a transcript stream (format of ald_batch_transcript_stream) turned into records the front end reads
+struct StreamRecords { std::vector<uint32_t> pool; std::vector<unsigned long long> roff; std::vector<double> cov; std::vector<int32_t> sid; std::vector<int64_t> label, tids; };
+int tx_stream_records(const uint32_t *words, int64_t n_words, const double *coverage, const int64_t *tid, int32_t skip_single_exon, int64_t graph_offset, StreamRecords &R);
+// a downloaded batch's path table in (graph, path) order on the device (b->d_ordoff), built once per download
+int device_path_table(ald_batch *b);
+
+// the reduced set of one batch, flat, in the reference's iteration order (ascending bucket hash, bucket order inside)
+struct ald_tset_flat {      // (rvec: sized once, every element written by the parallel fill -- no zero pass over ~200 MB first)
+    rvec<uint64_t> hash; rvec<int32_t> count, count1, count2; rvec<char> strand; rvec<double> coverage, cov2, conf, abd; rvec<int64_t> tid; std::vector<int64_t> exon_offset, sample_offset;
+    rvec<int32_t> exon_lr, sample_sid, sample_count1; rvec<double> sample_cov2, sample_conf, sample_abd;
+    double device_ms = 0, host_ms = 0; int64_t n_device_groups = 0, n_host_items = 0;
+};

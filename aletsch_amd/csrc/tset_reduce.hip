@@ -20,8 +20,7 @@
 //   tx_heads      1 lane / sorted   first member of a group?  (keys equal AND the compared words equal: a key collision splits, never fuses)
 //   tx_fold       1 lane / group    coverage in the reference's nesting, count, maxima, bounds
 //   tx_skeys / tx_sheads / tx_sfold    the per-sample copies: (group, sample) runs after a second stable sort, maxima per run
-#include "ald_internal.h"
-#include "../host/transcript_sink.hpp"
+#include "tset_front.h"
 #include <hipcub/hipcub.hpp>
 #include <cmath>
 #include <thread>
@@ -29,17 +28,6 @@
 #include <chrono>
 
 namespace {
-
-#define HCHK(x) do { hipError_t e_ = (x); if(e_ != hipSuccess) return ald_set_err(ALD_ERR_HIP, std::string(#x) + ": " + hipGetErrorString(e_)); } while(0)
-
-enum { TX_BLOCK = 256 };
-static const uint64_t TX_HOST = ~0ull;                 // key of a transcript the host merges (fewer than two exons)
-
-// The paths of a batch as the kernels see them: record offsets in (graph, path) order + the record pool.  A record carries the joined
-// exons of its transcript behind the vertex list (decomp_common.h), written by the decomposition kernel, so nothing here needs the
-// staged graphs or a host-side parse.
-struct TxIn { const unsigned long long *roff; const uint32_t *pool; int64_t np; };
-__host__ __device__ inline const int32_t *rec_exons(const uint32_t *r) { return (const int32_t*)(r + REC_HDR_WORDS + r[2]); }
 
 // ---- the result index in (graph, path) order: prefix of the per-graph path counts, then one lane per graph copies its entries
 __global__ void ix_order(const int32_t *n_paths, const int64_t *pbegin, const long long *graph_first, const unsigned long long *index, int n, unsigned long long *ordoff)
@@ -101,16 +89,16 @@ __global__ void tx_heads(TxIn in, const uint64_t *skey, const int64_t *sidx, int
     head[i] = (i == 0 || skey[i] != skey[i - 1] || !same_group(in, sidx[i - 1], sidx[i])) ? 1 : 0;
 }
 
-// first: path (in (graph, path) order) whose record the item takes its exons, strand and id from
-struct TxGroup { int64_t first; unsigned long long first_off; int32_t count, count1, lo, hi; double coverage, cov2, conf, abd; uint32_t bucket; int32_t nw, graph, path, strand, pad; };
-
-__global__ void tx_fold(TxIn in, const uint64_t *skey, const int64_t *sidx, const int32_t *head, const int32_t *gid, int64_t n_dev, const double *cov, TxGroup *out)
+// start_idx / start_cov (null for a set that starts empty): the resident item a group lands on -- its coverage is where the sum starts
+__global__ void tx_fold(TxIn in, const uint64_t *skey, const int64_t *sidx, const int32_t *head, const int32_t *gid, int64_t n_dev, const double *cov,
+                        const int64_t *start_idx, const double *start_cov, TxGroup *out)
 {
     const int64_t i = (int64_t)blockIdx.x * TX_BLOCK + threadIdx.x;
     if(i >= n_dev || !head[i]) return;
     TxGroup G; G.first = sidx[i]; G.first_off = in.roff[sidx[i]]; G.bucket = (uint32_t)(skey[i] >> 32); G.count = 0; G.count1 = 0; G.coverage = 0; G.cov2 = 0; G.conf = 0; G.abd = 0; G.lo = 0; G.hi = 0; G.pad = 0;
     { const uint32_t *r0 = in.pool + G.first_off; G.nw = (int32_t)r0[REC_NEXW]; G.graph = (int32_t)r0[0]; G.path = (int32_t)r0[1]; G.strand = (int32_t)(r0[5] & 0xFF); }
     double inner = 0; int cur_g = -1; bool any = false;
+    if(start_idx) { const int64_t z = start_idx[gid[i] - 1]; if(z >= 0) { G.coverage = start_cov[z]; any = true; } }
     for(int64_t m = i; m < n_dev && (m == i || !head[m]); m++) {
         const int64_t p = sidx[m]; const uint32_t *r = in.pool + in.roff[p];
         const int g = (int)r[0]; const double c = cov[p];
@@ -144,7 +132,6 @@ __global__ void tx_sheads(const uint64_t *skey2, int64_t n_dev, int32_t *head2)
     if(i >= n_dev) return;
     head2[i] = (i == 0 || skey2[i] != skey2[i - 1]) ? 1 : 0;
 }
-struct TxSample { int32_t gid, sid, count1, pad; double cov2, conf, abd; };
 __global__ void tx_sfold(TxIn in, const uint64_t *skey2, const int64_t *spos, const int64_t *sidx, const int32_t *head2, const int32_t *rid, int64_t n_dev, const double *cov, TxSample *out)
 {
     const int64_t i = (int64_t)blockIdx.x * TX_BLOCK + threadIdx.x;
@@ -190,17 +177,12 @@ __global__ void ts_emit(TxIn in, const int64_t *at, const int32_t *sid, uint32_t
     for(int q = l; q < k; q += 16) w[ALD_TS_HDR + q] = x[q];
 }
 
-inline unsigned grid_for(int64_t n) { return (unsigned)((n + TX_BLOCK - 1) / TX_BLOCK); }
-
-// scratch of a reduction (owned by a batch and kept across calls, or temporary for the stream entry point)
-struct RedScratch { DevBuf *red; PinBuf *pin; hipStream_t st; };
-
 } // namespace
 
 // The result index of a downloaded batch in (graph, path) order, in DEVICE memory: d_ordoff[path_begin[g] + p] = pool offset of record
 // (g, p).  Everything comes from what the decomposition kernel left in HBM -- the per-graph path counts, graph_first and the index
 // entries -- so the transcript stream and the set reduction start without any host-side table.
-static int device_path_table(ald_batch *b)
+int device_path_table(ald_batch *b)
 {
     if(b->paths_on_device) return ALD_OK;
     const int n = b->hb.n(); const int64_t np = b->total_paths;
@@ -219,12 +201,130 @@ static int device_path_table(ald_batch *b)
     return ALD_OK;
 }
 
-// the reduced set of one batch, flat, in the reference's iteration order (ascending bucket hash, bucket order inside)
-struct ald_tset_flat {      // (rvec: sized once, every element written by the parallel fill -- no zero pass over ~200 MB first)
-    rvec<uint64_t> hash; rvec<int32_t> count, count1, count2; rvec<char> strand; rvec<double> coverage, cov2, conf, abd; rvec<int64_t> tid; std::vector<int64_t> exon_offset, sample_offset;
-    rvec<int32_t> exon_lr, sample_sid, sample_count1; rvec<double> sample_cov2, sample_conf, sample_abd;
-    double device_ms = 0, host_ms = 0; int64_t n_device_groups = 0, n_host_items = 0;
-};
+int tx_front_groups(RedScratch S, TxIn in, const double *h_cov, int n_graphs, const int32_t *sid, TxFront &F)
+{
+    const int64_t np = in.np;
+    F.np = np; F.n_dev = 0; F.n_groups = 0; F.n_runs = 0; F.host_paths.clear(); F.sid_on_device = sid != nullptr;
+    if(np == 0) { if(F.ev0) HCHK(hipEventRecord(F.ev0, S.st)); return ALD_OK; }
+    DevBuf &d_cov = S.red[2], &d_nw = S.red[4], &d_key = S.red[5], &d_key2 = S.red[6], &d_idx = S.red[7], &d_idx2 = S.red[8], &d_graph = S.red[9],
+           &d_sid = S.red[10], &d_head = S.red[11], &d_gid = S.red[12], &d_tmp = S.red[14], &d_head2 = S.red[15], &d_rid = S.red[16], &d_pos = S.red[18], &d_pos2 = S.red[19];
+    PinBuf &p_key = S.pin[0];
+    if(p_key.ensure(8 * (size_t)np, true)) return ald_set_err(ALD_ERR_NOMEM, "pinned reduction buffers");
+    if(d_cov.ensure(8 * (size_t)np) || d_nw.ensure(4 * (size_t)np) || d_key.ensure(8 * (size_t)np)
+       || d_key2.ensure(8 * (size_t)np) || d_idx.ensure(8 * (size_t)np) || d_idx2.ensure(8 * (size_t)np) || d_graph.ensure(4 * (size_t)np) || d_head.ensure(4 * (size_t)np) || d_gid.ensure(4 * (size_t)np)
+       || d_head2.ensure(4 * (size_t)np) || d_rid.ensure(4 * (size_t)np) || d_pos.ensure(8 * (size_t)np) || d_pos2.ensure(8 * (size_t)np) || (sid && d_sid.ensure(4 * (size_t)n_graphs + 4))) return ald_set_err(ALD_ERR_NOMEM, "reduction buffers");
+    hipStream_t st = S.st;
+    HCHK(hipMemcpyAsync(d_cov.p, h_cov, 8 * (size_t)np, hipMemcpyHostToDevice, st));
+    if(sid) HCHK(hipMemcpyAsync(d_sid.p, sid, 4 * (size_t)n_graphs, hipMemcpyHostToDevice, st));
+    if(F.ev0) HCHK(hipEventRecord(F.ev0, st));
+    hipLaunchKernelGGL(tx_build, dim3(grid_for(np)), dim3(TX_BLOCK), 0, st, in, (int32_t*)d_nw.p, (uint64_t*)d_key.p, (int32_t*)d_graph.p);
+    hipLaunchKernelGGL(tx_iota, dim3(grid_for(np)), dim3(TX_BLOCK), 0, st, (int64_t*)d_idx.p, np);
+    // stable sort by group key: members of a group stay in (graph, path) order; host-side transcripts (key = ~0) sink to the end
+    size_t tmp_bytes = 0;
+    HCHK(hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_bytes, (const uint64_t*)d_key.p, (uint64_t*)d_key2.p, (const int64_t*)d_idx.p, (int64_t*)d_idx2.p, (int)np, 0, 64, st));
+    size_t scan_bytes = 0;
+    HCHK(hipcub::DeviceScan::InclusiveSum(nullptr, scan_bytes, (const int32_t*)d_head.p, (int32_t*)d_gid.p, (int)np, st));
+    if(d_tmp.ensure(std::max(tmp_bytes, scan_bytes) + 256)) return ald_set_err(ALD_ERR_NOMEM, "sort scratch");
+    HCHK(hipcub::DeviceRadixSort::SortPairs(d_tmp.p, tmp_bytes, (const uint64_t*)d_key.p, (uint64_t*)d_key2.p, (const int64_t*)d_idx.p, (int64_t*)d_idx2.p, (int)np, 0, 64, st));
+    // how many went to the device: the sorted keys below TX_HOST
+    const uint64_t *h_key = (const uint64_t*)p_key.p;
+    HCHK(hipMemcpyAsync(p_key.p, d_key2.p, 8 * (size_t)np, hipMemcpyDeviceToHost, st));
+    HCHK(hipStreamSynchronize(st));
+    const int64_t n_dev = (int64_t)(std::lower_bound(h_key, h_key + np, TX_HOST) - h_key);
+    F.n_dev = n_dev;
+    if(n_dev > 0) {
+        hipLaunchKernelGGL(tx_heads, dim3(grid_for(n_dev)), dim3(TX_BLOCK), 0, st, in, (const uint64_t*)d_key2.p, (const int64_t*)d_idx2.p, n_dev, (int32_t*)d_head.p);
+        HCHK(hipcub::DeviceScan::InclusiveSum(d_tmp.p, scan_bytes, (const int32_t*)d_head.p, (int32_t*)d_gid.p, (int)n_dev, st));
+        HCHK(hipMemcpyAsync(&F.n_groups, (int32_t*)d_gid.p + (n_dev - 1), 4, hipMemcpyDeviceToHost, st));
+    }
+    // the transcripts left to the host: the tail of the sorted order (key TX_HOST; the stable sort kept them in (graph, path) order)
+    F.host_paths.resize((size_t)(np - n_dev));
+    if(np > n_dev) HCHK(hipMemcpyAsync(F.host_paths.data(), (const int64_t*)d_idx2.p + n_dev, 8 * (size_t)(np - n_dev), hipMemcpyDeviceToHost, st));
+    HCHK(hipStreamSynchronize(st));
+    if(hipGetLastError() != hipSuccess) return ald_set_err(ALD_ERR_HIP, "a reduction kernel failed to launch");
+    return ALD_OK;
+}
+
+int tx_front_fold(RedScratch S, TxIn in, TxFront &F, const int64_t *start_idx, const double *start_cov)
+{
+    const int64_t n_dev = F.n_dev; F.n_runs = 0;
+    if(n_dev == 0) return ALD_OK;
+    DevBuf &d_cov = S.red[2], &d_key = S.red[5], &d_idx = S.red[7], &d_graph = S.red[9], &d_sid = S.red[10], &d_groups = S.red[13], &d_tmp = S.red[14],
+           &d_head2 = S.red[15], &d_rid = S.red[16], &d_samples = S.red[17], &d_pos = S.red[18], &d_pos2 = S.red[19];
+    hipStream_t st = S.st;
+    const uint64_t *skey = tx_skey(S); const int64_t *sidx = tx_sidx(S);
+    if(d_groups.ensure(sizeof(TxGroup) * (size_t)F.n_groups)) return ald_set_err(ALD_ERR_NOMEM, "group records");
+    hipLaunchKernelGGL(tx_fold, dim3(grid_for(n_dev)), dim3(TX_BLOCK), 0, st, in, skey, sidx, tx_head(S), tx_gid(S), n_dev, (const double*)d_cov.p, start_idx, start_cov, (TxGroup*)d_groups.p);
+    // per-sample copies: second stable sort by (group, sample)
+    hipLaunchKernelGGL(tx_skeys, dim3(grid_for(n_dev)), dim3(TX_BLOCK), 0, st, sidx, tx_gid(S), (const int32_t*)d_graph.p, F.sid_on_device ? (const int32_t*)d_sid.p : (const int32_t*)nullptr, n_dev, (uint64_t*)d_key.p);
+    hipLaunchKernelGGL(tx_iota, dim3(grid_for(n_dev)), dim3(TX_BLOCK), 0, st, (int64_t*)d_pos.p, n_dev);
+    size_t tmp_bytes = 0, scan_bytes = 0;
+    HCHK(hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_bytes, (const uint64_t*)d_key.p, (uint64_t*)d_idx.p, (const int64_t*)d_pos.p, (int64_t*)d_pos2.p, (int)n_dev, 0, 64, st));
+    HCHK(hipcub::DeviceScan::InclusiveSum(nullptr, scan_bytes, (const int32_t*)d_head2.p, (int32_t*)d_rid.p, (int)n_dev, st));
+    if(d_tmp.ensure(std::max(tmp_bytes, scan_bytes) + 256)) return ald_set_err(ALD_ERR_NOMEM, "sort scratch");
+    HCHK(hipcub::DeviceRadixSort::SortPairs(d_tmp.p, tmp_bytes, (const uint64_t*)d_key.p, (uint64_t*)d_idx.p /* sorted key2 */, (const int64_t*)d_pos.p, (int64_t*)d_pos2.p, (int)n_dev, 0, 64, st));
+    hipLaunchKernelGGL(tx_sheads, dim3(grid_for(n_dev)), dim3(TX_BLOCK), 0, st, (const uint64_t*)d_idx.p, n_dev, (int32_t*)d_head2.p);
+    HCHK(hipcub::DeviceScan::InclusiveSum(d_tmp.p, scan_bytes, (const int32_t*)d_head2.p, (int32_t*)d_rid.p, (int)n_dev, st));
+    HCHK(hipMemcpyAsync(&F.n_runs, (int32_t*)d_rid.p + (n_dev - 1), 4, hipMemcpyDeviceToHost, st));
+    HCHK(hipStreamSynchronize(st));
+    if(d_samples.ensure(sizeof(TxSample) * (size_t)F.n_runs)) return ald_set_err(ALD_ERR_NOMEM, "sample records");
+    hipLaunchKernelGGL(tx_sfold, dim3(grid_for(n_dev)), dim3(TX_BLOCK), 0, st, in, (const uint64_t*)d_idx.p, (const int64_t*)d_pos2.p, sidx, (const int32_t*)d_head2.p, (const int32_t*)d_rid.p, n_dev,
+                       (const double*)d_cov.p, (TxSample*)d_samples.p);
+    if(hipGetLastError() != hipSuccess) return ald_set_err(ALD_ERR_HIP, "a reduction kernel failed to launch");
+    return ALD_OK;
+}
+
+void tx_host_singles(aletsch::transcript_sink &into, const std::vector<int64_t> &host_paths, const uint32_t *h_pool, const unsigned long long *h_roff,
+                     const double *h_cov, const int64_t *h_tid, const int32_t *sid, const int64_t *label, int64_t tid_base)
+{
+    // one without any exon lands in bucket 0, as get_intron_chain_hashing puts it
+    aletsch::sink_transcript x;
+    auto fill = [&](int64_t p) {
+        const uint32_t *r = h_pool + h_roff[(size_t)p]; const int g = (int)r[0];
+        double conf, abd; memcpy(&abd, r + 8, 8); memcpy(&conf, r + 10, 8);
+        x.strand = (char)(r[5] & 0xFF); x.coverage = h_cov[(size_t)p]; x.top.cov2 = x.coverage; x.top.conf = conf; x.top.abd = abd; x.top.count1 = (int32_t)r[4]; x.count2 = 1;
+        x.tid = h_tid ? h_tid[(size_t)p] : tid_base + (((label ? label[g] : (int64_t)g) << 20) | (int64_t)r[1]);
+        const int32_t *ex = rec_exons(r); x.xs.assign(ex, ex + r[REC_NEXW]);
+    };
+    for(size_t a = 0; a < host_paths.size(); ) {          // one per-graph set per graph that has any (assembler.cc:1105-1133)
+        const int g = (int)h_pool[h_roff[(size_t)host_paths[a]]];
+        size_t e = a; while(e < host_paths.size() && (int)h_pool[h_roff[(size_t)host_paths[e]]] == g) e++;
+        if(e - a == 1) { fill(host_paths[a]); into.add(x, 1, sid ? sid[g] : -1); }   // merging a one-item set is the same as adding the item (transcript_set.cc:149-175)
+        else {
+            aletsch::transcript_sink ts(into.single_exon_overlap());
+            for(size_t q = a; q < e; q++) { fill(host_paths[q]); ts.add(x, 1, sid ? sid[g] : -1); }
+            into.add(ts);
+        }
+        a = e;
+    }
+}
+
+// A transcript stream as records of a scratch pool (header + two placeholder vertices + the exon words), groups re-numbered 0 .. G-1 in
+// stream order; label[g] = the stream's graph id + graph_offset.  Single-exon transcripts are left out when skip_single_exon.
+int tx_stream_records(const uint32_t *words, int64_t n_words, const double *coverage, const int64_t *tid, int32_t skip_single_exon, int64_t graph_offset, StreamRecords &R)
+{
+    std::vector<uint32_t> &pool = R.pool; std::vector<unsigned long long> &roff = R.roff; std::vector<double> &cov = R.cov; std::vector<int32_t> &sid = R.sid; std::vector<int64_t> &label = R.label, &tids = R.tids;
+    int64_t last = -1, ti = -1;                            // ti: ordinal of the transcript in the stream (index into `coverage`)
+    for(int64_t o = 0; o < n_words; ) {
+        ti++;
+        if(o + ALD_TS_HDR > n_words) return ald_set_err(ALD_ERR_INVALID, "malformed transcript stream");
+        const int64_t k = 2 * (int64_t)words[o + 5], len = ALD_TS_HDR + k;
+        if((int32_t)words[o + 5] < 0 || o + len > n_words) return ald_set_err(ALD_ERR_INVALID, "malformed transcript stream");
+        const int64_t g = (int64_t)words[o];
+        if(g < last) return ald_set_err(ALD_ERR_INVALID, "transcript stream not in ascending graph order");
+        if(g != last) { label.push_back(g + graph_offset); sid.push_back((int32_t)words[o + 2]); last = g; }
+        if(skip_single_exon && k <= 2) { o += len; continue; }
+        const size_t at = pool.size(); roff.push_back((unsigned long long)at);
+        pool.resize(at + (size_t)rec_words(2, (unsigned)k), 0);
+        uint32_t *r = pool.data() + at;
+        r[0] = (uint32_t)(label.size() - 1); r[1] = words[o + 1]; r[2] = 2; r[3] = 0; r[4] = words[o + 4]; r[5] = words[o + 3] & 0xFF;
+        r[6] = words[o + 6]; r[7] = words[o + 7]; r[8] = words[o + 10]; r[9] = words[o + 11]; r[10] = words[o + 8]; r[11] = words[o + 9]; r[12] = r[13] = 0; r[REC_NEXW] = (uint32_t)k; r[REC_NEXW + 1] = 0;
+        memcpy(r + REC_HDR_WORDS + 2, words + o + ALD_TS_HDR, 4 * (size_t)k);
+        double w; memcpy(&w, words + o + 6, 8); cov.push_back(coverage ? coverage[ti] : log(1.0 + w)); if(tid) tids.push_back(tid[ti]);
+        o += len;
+    }
+    return ALD_OK;
+}
 
 namespace {
 struct EventPair { hipEvent_t a = nullptr, b = nullptr; ~EventPair() { if(a) hipEventDestroy(a); if(b) hipEventDestroy(b); } };
@@ -241,64 +341,22 @@ int reduce_core(RedScratch S, const uint32_t *d_pool, const unsigned long long *
     const auto T1 = std::chrono::steady_clock::now();
     // what comes back from the device lands in pinned buffers kept across calls (pageable targets would halve the copy rate, and the
     // device scratch is not reallocated call after call either)
-    int64_t n_dev = 0; size_t NGd = 0, NSd = 0; std::vector<int64_t> host_paths;
-    const TxGroup *groups = nullptr; const TxSample *samples = nullptr; const uint64_t *h_key = nullptr;
+    size_t NGd = 0, NSd = 0; TxFront X;
+    const TxGroup *groups = nullptr; const TxSample *samples = nullptr;
     if(np > 0) {
-        DevBuf &d_cov = S.red[2], &d_nw = S.red[4], &d_key = S.red[5], &d_key2 = S.red[6], &d_idx = S.red[7], &d_idx2 = S.red[8], &d_graph = S.red[9],
-               &d_sid = S.red[10], &d_head = S.red[11], &d_gid = S.red[12], &d_groups = S.red[13], &d_tmp = S.red[14], &d_head2 = S.red[15], &d_rid = S.red[16], &d_samples = S.red[17], &d_pos = S.red[18], &d_pos2 = S.red[19];
-        PinBuf &p_key = S.pin[0], &p_groups = S.pin[1], &p_samples = S.pin[2];
-        if(p_key.ensure(8 * (size_t)np, true)) return ald_set_err(ALD_ERR_NOMEM, "pinned reduction buffers");
-        if(d_cov.ensure(8 * (size_t)np) || d_nw.ensure(4 * (size_t)np) || d_key.ensure(8 * (size_t)np)
-           || d_key2.ensure(8 * (size_t)np) || d_idx.ensure(8 * (size_t)np) || d_idx2.ensure(8 * (size_t)np) || d_graph.ensure(4 * (size_t)np) || d_head.ensure(4 * (size_t)np) || d_gid.ensure(4 * (size_t)np)
-           || d_head2.ensure(4 * (size_t)np) || d_rid.ensure(4 * (size_t)np) || d_pos.ensure(8 * (size_t)np) || d_pos2.ensure(8 * (size_t)np) || (sid && d_sid.ensure(4 * (size_t)n_graphs + 4))) return ald_set_err(ALD_ERR_NOMEM, "reduction buffers");
+        PinBuf &p_groups = S.pin[1], &p_samples = S.pin[2];
         hipStream_t st = S.st;
-        HCHK(hipMemcpyAsync(d_cov.p, h_cov, 8 * (size_t)np, hipMemcpyHostToDevice, st));
-        if(sid) HCHK(hipMemcpyAsync(d_sid.p, sid, 4 * (size_t)n_graphs, hipMemcpyHostToDevice, st));
         EventPair ev; HCHK(hipEventCreate(&ev.a)); HCHK(hipEventCreate(&ev.b));
-        HCHK(hipEventRecord(ev.a, st));
         TxIn in; in.roff = d_roff; in.pool = d_pool; in.np = np;
-        hipLaunchKernelGGL(tx_build, dim3(grid_for(np)), dim3(TX_BLOCK), 0, st, in, (int32_t*)d_nw.p, (uint64_t*)d_key.p, (int32_t*)d_graph.p);
-        hipLaunchKernelGGL(tx_iota, dim3(grid_for(np)), dim3(TX_BLOCK), 0, st, (int64_t*)d_idx.p, np);
-        // stable sort by group key: members of a group stay in (graph, path) order; host-side transcripts (key = ~0) sink to the end
-        size_t tmp_bytes = 0;
-        HCHK(hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_bytes, (const uint64_t*)d_key.p, (uint64_t*)d_key2.p, (const int64_t*)d_idx.p, (int64_t*)d_idx2.p, (int)np, 0, 64, st));
-        size_t scan_bytes = 0;
-        HCHK(hipcub::DeviceScan::InclusiveSum(nullptr, scan_bytes, (const int32_t*)d_head.p, (int32_t*)d_gid.p, (int)np, st));
-        if(d_tmp.ensure(std::max(tmp_bytes, scan_bytes) + 256)) return ald_set_err(ALD_ERR_NOMEM, "sort scratch");
-        HCHK(hipcub::DeviceRadixSort::SortPairs(d_tmp.p, tmp_bytes, (const uint64_t*)d_key.p, (uint64_t*)d_key2.p, (const int64_t*)d_idx.p, (int64_t*)d_idx2.p, (int)np, 0, 64, st));
-        // how many went to the device: the sorted keys below TX_HOST
-        h_key = (const uint64_t*)p_key.p;
-        HCHK(hipMemcpyAsync(p_key.p, d_key2.p, 8 * (size_t)np, hipMemcpyDeviceToHost, st));
-        HCHK(hipStreamSynchronize(st));
-        n_dev = (int64_t)(std::lower_bound(h_key, h_key + np, TX_HOST) - h_key);
-        int32_t n_groups = 0, n_runs = 0;
-        if(n_dev > 0) {
-            const uint64_t *skey = (const uint64_t*)d_key2.p; const int64_t *sidx = (const int64_t*)d_idx2.p;
-            hipLaunchKernelGGL(tx_heads, dim3(grid_for(n_dev)), dim3(TX_BLOCK), 0, st, in, skey, sidx, n_dev, (int32_t*)d_head.p);
-            HCHK(hipcub::DeviceScan::InclusiveSum(d_tmp.p, scan_bytes, (const int32_t*)d_head.p, (int32_t*)d_gid.p, (int)n_dev, st));
-            HCHK(hipMemcpyAsync(&n_groups, (int32_t*)d_gid.p + (n_dev - 1), 4, hipMemcpyDeviceToHost, st));
-            HCHK(hipStreamSynchronize(st));
-            if(d_groups.ensure(sizeof(TxGroup) * (size_t)n_groups)) return ald_set_err(ALD_ERR_NOMEM, "group records");
-            hipLaunchKernelGGL(tx_fold, dim3(grid_for(n_dev)), dim3(TX_BLOCK), 0, st, in, skey, sidx, (const int32_t*)d_head.p, (const int32_t*)d_gid.p, n_dev, (const double*)d_cov.p, (TxGroup*)d_groups.p);
-            // per-sample copies: second stable sort by (group, sample)
-            hipLaunchKernelGGL(tx_skeys, dim3(grid_for(n_dev)), dim3(TX_BLOCK), 0, st, sidx, (const int32_t*)d_gid.p, (const int32_t*)d_graph.p, sid ? (const int32_t*)d_sid.p : (const int32_t*)nullptr, n_dev, (uint64_t*)d_key.p);
-            hipLaunchKernelGGL(tx_iota, dim3(grid_for(n_dev)), dim3(TX_BLOCK), 0, st, (int64_t*)d_pos.p, n_dev);
-            HCHK(hipcub::DeviceRadixSort::SortPairs(d_tmp.p, tmp_bytes, (const uint64_t*)d_key.p, (uint64_t*)d_idx.p /* sorted key2 */, (const int64_t*)d_pos.p, (int64_t*)d_pos2.p, (int)n_dev, 0, 64, st));
-            hipLaunchKernelGGL(tx_sheads, dim3(grid_for(n_dev)), dim3(TX_BLOCK), 0, st, (const uint64_t*)d_idx.p, n_dev, (int32_t*)d_head2.p);
-            HCHK(hipcub::DeviceScan::InclusiveSum(d_tmp.p, scan_bytes, (const int32_t*)d_head2.p, (int32_t*)d_rid.p, (int)n_dev, st));
-            HCHK(hipMemcpyAsync(&n_runs, (int32_t*)d_rid.p + (n_dev - 1), 4, hipMemcpyDeviceToHost, st));
-            HCHK(hipStreamSynchronize(st));
-            if(d_samples.ensure(sizeof(TxSample) * (size_t)n_runs)) return ald_set_err(ALD_ERR_NOMEM, "sample records");
-            hipLaunchKernelGGL(tx_sfold, dim3(grid_for(n_dev)), dim3(TX_BLOCK), 0, st, in, (const uint64_t*)d_idx.p, (const int64_t*)d_pos2.p, sidx, (const int32_t*)d_head2.p, (const int32_t*)d_rid.p, n_dev,
-                               (const double*)d_cov.p, (TxSample*)d_samples.p);
-            if(p_groups.ensure(sizeof(TxGroup) * (size_t)n_groups, true) || p_samples.ensure(sizeof(TxSample) * (size_t)n_runs, true)) return ald_set_err(ALD_ERR_NOMEM, "pinned reduction buffers");
-            NGd = (size_t)n_groups; NSd = (size_t)n_runs; groups = (const TxGroup*)p_groups.p; samples = (const TxSample*)p_samples.p;
-            HCHK(hipMemcpyAsync(p_groups.p, d_groups.p, sizeof(TxGroup) * (size_t)n_groups, hipMemcpyDeviceToHost, st));
-            HCHK(hipMemcpyAsync(p_samples.p, d_samples.p, sizeof(TxSample) * (size_t)n_runs, hipMemcpyDeviceToHost, st));
+        X.ev0 = ev.a;
+        { int rc = tx_front_groups(S, in, h_cov, n_graphs, sid, X); if(rc != ALD_OK) return rc; }
+        if(X.n_dev > 0) {
+            { int rc = tx_front_fold(S, in, X, nullptr, nullptr); if(rc != ALD_OK) return rc; }
+            if(p_groups.ensure(sizeof(TxGroup) * (size_t)X.n_groups, true) || p_samples.ensure(sizeof(TxSample) * (size_t)X.n_runs, true)) return ald_set_err(ALD_ERR_NOMEM, "pinned reduction buffers");
+            NGd = (size_t)X.n_groups; NSd = (size_t)X.n_runs; groups = (const TxGroup*)p_groups.p; samples = (const TxSample*)p_samples.p;
+            HCHK(hipMemcpyAsync(p_groups.p, tx_groups(S), sizeof(TxGroup) * NGd, hipMemcpyDeviceToHost, st));
+            HCHK(hipMemcpyAsync(p_samples.p, tx_samples(S), sizeof(TxSample) * NSd, hipMemcpyDeviceToHost, st));
         }
-        // the transcripts left to the host: the tail of the sorted order (key TX_HOST; the stable sort kept them in (graph, path) order)
-        host_paths.resize((size_t)(np - n_dev));
-        if(np > n_dev) HCHK(hipMemcpyAsync(host_paths.data(), (const int64_t*)d_idx2.p + n_dev, 8 * (size_t)(np - n_dev), hipMemcpyDeviceToHost, st));
         HCHK(hipEventRecord(ev.b, st));
         HCHK(hipStreamSynchronize(st));
         float ms = 0; hipEventElapsedTime(&ms, ev.a, ev.b); F->device_ms = ms;
@@ -306,30 +364,9 @@ int reduce_core(RedScratch S, const uint32_t *d_pool, const unsigned long long *
     }
     const auto T2 = std::chrono::steady_clock::now();
     auto graph_label = [&](int g) -> int64_t { return label ? label[g] : (int64_t)g; };
-    // ---- host: transcripts with fewer than two exons through the sink (their overlap rule depends on the order of the comparisons;
-    // one without any exon lands in bucket 0, as get_intron_chain_hashing puts it)
+    // ---- host: transcripts with fewer than two exons through the sink (their overlap rule depends on the order of the comparisons)
     aletsch::transcript_sink single(single_exon_overlap);
-    {
-        aletsch::sink_transcript x;
-        auto fill = [&](int64_t p) {
-            const uint32_t *r = h_pool + h_roff[(size_t)p]; const int g = (int)r[0];
-            double conf, abd; memcpy(&abd, r + 8, 8); memcpy(&conf, r + 10, 8);
-            x.strand = (char)(r[5] & 0xFF); x.coverage = h_cov[(size_t)p]; x.top.cov2 = x.coverage; x.top.conf = conf; x.top.abd = abd; x.top.count1 = (int32_t)r[4]; x.count2 = 1;
-            x.tid = h_tid ? h_tid[(size_t)p] : tid_base + ((graph_label(g) << 20) | (int64_t)r[1]);
-            const int32_t *ex = rec_exons(r); x.xs.assign(ex, ex + r[REC_NEXW]);
-        };
-        for(size_t a = 0; a < host_paths.size() && !skip_single_exon; ) {          // one per-graph set per graph that has any (assembler.cc:1105-1133)
-            const int g = (int)h_pool[h_roff[(size_t)host_paths[a]]];
-            size_t e = a; while(e < host_paths.size() && (int)h_pool[h_roff[(size_t)host_paths[e]]] == g) e++;
-            if(e - a == 1) { fill(host_paths[a]); single.add(x, 1, sid ? sid[g] : -1); }   // merging a one-item set is the same as adding the item (transcript_set.cc:149-175)
-            else {
-                aletsch::transcript_sink ts(single_exon_overlap);
-                for(size_t q = a; q < e; q++) { fill(host_paths[q]); ts.add(x, 1, sid ? sid[g] : -1); }
-                single.add(ts);
-            }
-            a = e;
-        }
-    }
+    if(!skip_single_exon) tx_host_singles(single, X.host_paths, h_pool, h_roff, h_cov, h_tid, sid, label, tid_base);
     const auto T3 = std::chrono::steady_clock::now();
     // ---- host: the flat set.  Device groups arrive in ascending (bucket, key) order, i.e. in the reference's iteration order already;
     // what is left is (i) groups that share a bucket (a 31-bit hash collision): compare1 order among themselves, (ii) the few host
@@ -425,27 +462,9 @@ int ald_tset_reduce_stream(int32_t device, const uint32_t *words, int64_t n_word
     if(hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return ald_set_err(ALD_ERR_NO_DEVICE, "no HIP device visible: the reduction has no CPU fallback");
     if(device < 0 || device >= ndev) return ald_set_err(ALD_ERR_INVALID, "device index out of range");
     HCHK(hipSetDevice(device));
-    // records: header + two placeholder vertices + the exon words; groups re-numbered 0 .. G-1 in stream order
-    std::vector<uint32_t> pool; std::vector<unsigned long long> roff; std::vector<double> cov; std::vector<int32_t> sid; std::vector<int64_t> label, tids;
-    int64_t last = -1, ti = -1;                            // ti: ordinal of the transcript in the stream (index into `coverage`)
-    for(int64_t o = 0; o < n_words; ) {
-        ti++;
-        if(o + ALD_TS_HDR > n_words) return ald_set_err(ALD_ERR_INVALID, "malformed transcript stream");
-        const int64_t k = 2 * (int64_t)words[o + 5], len = ALD_TS_HDR + k;
-        if((int32_t)words[o + 5] < 0 || o + len > n_words) return ald_set_err(ALD_ERR_INVALID, "malformed transcript stream");
-        const int64_t g = (int64_t)words[o];
-        if(g < last) return ald_set_err(ALD_ERR_INVALID, "transcript stream not in ascending graph order");
-        if(g != last) { label.push_back(g); sid.push_back((int32_t)words[o + 2]); last = g; }
-        if(skip_single_exon && k <= 2) { o += len; continue; }
-        const size_t at = pool.size(); roff.push_back((unsigned long long)at);
-        pool.resize(at + (size_t)rec_words(2, (unsigned)k), 0);
-        uint32_t *r = pool.data() + at;
-        r[0] = (uint32_t)(label.size() - 1); r[1] = words[o + 1]; r[2] = 2; r[3] = 0; r[4] = words[o + 4]; r[5] = words[o + 3] & 0xFF;
-        r[6] = words[o + 6]; r[7] = words[o + 7]; r[8] = words[o + 10]; r[9] = words[o + 11]; r[10] = words[o + 8]; r[11] = words[o + 9]; r[12] = r[13] = 0; r[REC_NEXW] = (uint32_t)k; r[REC_NEXW + 1] = 0;
-        memcpy(r + REC_HDR_WORDS + 2, words + o + ALD_TS_HDR, 4 * (size_t)k);
-        double w; memcpy(&w, words + o + 6, 8); cov.push_back(coverage ? coverage[ti] : log(1.0 + w)); if(tid) tids.push_back(tid[ti]);
-        o += len;
-    }
+    StreamRecords R;
+    { int rc = tx_stream_records(words, n_words, coverage, tid, skip_single_exon, 0, R); if(rc != ALD_OK) return rc; }
+    std::vector<uint32_t> &pool = R.pool; std::vector<unsigned long long> &roff = R.roff; std::vector<double> &cov = R.cov; std::vector<int32_t> &sid = R.sid; std::vector<int64_t> &label = R.label, &tids = R.tids;
     const int64_t np = (int64_t)roff.size();
     DevBuf red[20], d_pool, d_roff; PinBuf pin[8];
     struct Rel { DevBuf *r, *a, *c; PinBuf *p; ~Rel() { for(int i = 0; i < 20; i++) r[i].release(); a->release(); c->release(); for(int i = 0; i < 8; i++) p[i].release(); } } rel{red, &d_pool, &d_roff, pin};

@@ -1,0 +1,581 @@
+// tset_resident.hip -- a transcript set that lives in HBM: batches (or transcript streams) fold into it on the device, call after call,
+// and it leaves the device only when the caller asks (ald_tset_dev_*).
+//
+// What it replaces: the region's `tm` of meta/assembler.cc:1105-1133 -- per graph ts.add(t, 1, sid), then tm.add(ts) into a set that is
+// NOT empty (rnacore/transcript_set.cc:149-175) -- and transcript_set::add(transcript_set&) between two such sets.  tset_reduce.hip
+// folds a batch into an EMPTY set; here the batch's groups meet the resident items, which changes exactly one thing: a group that lands
+// on a resident item of coverage c sums ((c + s1) + s2) + ..., not c + (s1 + s2 + ...), so the fold starts from the resident value.
+// Everything else a merge computes (counts, maxima, bounds, the union of the per-sample maps) does not depend on the order.
+//
+// Layout: structure of arrays sorted by (bucket hash, compare1), exons and samples as CSR (samples sorted by sid; count2 and the
+// per-sample coverage are derived: #samples and the item's coverage, transcript_set.cc:70-74).  Two buffer sets: every add writes the
+// other one and swaps, so a failed allocation leaves the set as it was.  Transcripts with fewer than two exons merge by an overlap test
+// that is not transitive; they stay in a host transcript_sink inside the set, fed graph by graph, and are spliced in by hash on export.
+//
+// One add (HBM-bound streaming passes; one lane per item):
+//   front end (tset_reduce.hip: tx_build, radix sort, tx_heads)   the batch's multi-exon groups
+//   rs_ghead / rs_order    groups in (bucket, compare1) order: the sort key orders by bucket; a lane per equal-bucket run sorts it
+//   rs_match               binary search on the resident hashes, then a compare1 walk inside the bucket: match or insertion point
+//   tx_fold (with start)   coverage from the matched item's value in (graph, path) order; tx_sfold: per-sample maxima
+//   rs_mark / scans / rs_slots   merge path: resident i -> i + #new before it, new j -> insertion point + #new before j
+//   rs_sizes / scans / rs_write  exon and sample counts per output item, prefix sums, then one gather pass into the other buffer set
+// ald_tset_dev_merge runs the same merge path with a second resident set as the incoming side (coverage c_dst + c_src).
+#include "tset_front.h"
+#include <hipcub/hipcub.hpp>
+#include <algorithm>
+#include <chrono>
+#include <memory>
+
+namespace {
+
+struct SetView {                     // one buffer set as the kernels see it (n items)
+    uint64_t *hash; int32_t *count; int8_t *strand; double *cov, *cov2, *conf, *abd; int32_t *count1; int64_t *tid;
+    int64_t *eoff; int32_t *lr;      // exons of item i: lr[2 * eoff[i] .. 2 * eoff[i + 1]) (l, r pairs)
+    int64_t *soff; int32_t *ssid, *sc1; double *scov2, *sconf, *sabd;      // samples of item i: [soff[i], soff[i + 1]), ascending sid
+    int64_t n;
+};
+
+struct SetBufs {
+    DevBuf hash, count, strand, cov, cov2, conf, abd, count1, tid, eoff, lr, soff, ssid, sc1, scov2, sconf, sabd;
+    int64_t n = 0, ne = 0, ns = 0;   // items, exons, samples
+    SetView view() {
+        SetView v; v.hash = (uint64_t*)hash.p; v.count = (int32_t*)count.p; v.strand = (int8_t*)strand.p; v.cov = (double*)cov.p; v.cov2 = (double*)cov2.p; v.conf = (double*)conf.p;
+        v.abd = (double*)abd.p; v.count1 = (int32_t*)count1.p; v.tid = (int64_t*)tid.p; v.eoff = (int64_t*)eoff.p; v.lr = (int32_t*)lr.p; v.soff = (int64_t*)soff.p;
+        v.ssid = (int32_t*)ssid.p; v.sc1 = (int32_t*)sc1.p; v.scov2 = (double*)scov2.p; v.sconf = (double*)sconf.p; v.sabd = (double*)sabd.p; v.n = n; return v;
+    }
+    int ensure_items(int64_t k) {    // k items (+1 offset entry)
+        const size_t m = (size_t)k + 1;
+        return hash.ensure(8 * m) || count.ensure(4 * m) || strand.ensure(m) || cov.ensure(8 * m) || cov2.ensure(8 * m) || conf.ensure(8 * m) || abd.ensure(8 * m)
+               || count1.ensure(4 * m) || tid.ensure(8 * m) || eoff.ensure(8 * m) || soff.ensure(8 * m);
+    }
+    int ensure_tail(int64_t n_exons, int64_t n_samples) {
+        const size_t e = (size_t)n_exons + 1, s = (size_t)n_samples + 1;
+        return lr.ensure(8 * e) || ssid.ensure(4 * s) || sc1.ensure(4 * s) || scov2.ensure(8 * s) || sconf.ensure(8 * s) || sabd.ensure(8 * s);
+    }
+    void release() { DevBuf *all[] = {&hash, &count, &strand, &cov, &cov2, &conf, &abd, &count1, &tid, &eoff, &lr, &soff, &ssid, &sc1, &scov2, &sconf, &sabd}; for(DevBuf *d : all) d->release(); n = ne = ns = 0; }
+};
+
+// transcript::compare1 for two chains of >= 2 exons (transcript.cc:269-300): +1 when a sorts first, -1 when b does, 0 equal.  The
+// words looked at: 1, 2 .. nw-5, nw-2 (intron_chain_compare stops one exon early and never sees the outer bounds, transcript.cc:218-238)
+__device__ inline int cmp1(int na, int sa, const int32_t *xa, int nb, int sb, const int32_t *xb)
+{
+    if(na != nb) return na < nb ? 1 : -1;
+    if(sa != sb) return sa < sb ? 1 : -1;
+    if(xa[1] != xb[1]) return xa[1] < xb[1] ? 1 : -1;
+    for(int k = 2; k + 5 <= na; k++) if(xa[k] != xb[k]) return xa[k] < xb[k] ? 1 : -1;
+    if(xa[na - 2] != xb[na - 2]) return xa[na - 2] < xb[na - 2] ? 1 : -1;
+    return 0;
+}
+__device__ inline int rec_strand(const uint32_t *r) { return (int)(int8_t)(r[5] & 0xFF); }      // the reference's `char` strand
+
+// The incoming side of a merge, two kinds with one interface.  j: position in (hash, compare1) order.
+struct InBatch {                     // a batch's groups: before the fold only hash / nw / strand / x are valid (they come from the records)
+    TxIn in; const int64_t *sidx; const int32_t *ghead; const uint64_t *skey; const int32_t *perm;
+    const TxGroup *grp; const TxSample *smp; const int64_t *sbeg;
+    int64_t tid_base; const int64_t *label, *ptid; int64_t n;
+    __device__ const uint32_t *rec(int64_t j) const { return in.pool + in.roff[sidx[ghead[perm[j]]]]; }
+    __device__ uint64_t hash(int64_t j) const { return skey[ghead[perm[j]]] >> 32; }
+    __device__ int nw(int64_t j) const { return (int)rec(j)[REC_NEXW]; }
+    __device__ int strand(int64_t j) const { return rec_strand(rec(j)); }
+    __device__ const int32_t *x(int64_t j) const { return rec_exons(rec(j)); }
+    __device__ int32_t lo(int64_t j) const { return grp[perm[j]].lo; }
+    __device__ int32_t hi(int64_t j) const { return grp[perm[j]].hi; }
+    __device__ int32_t count(int64_t j) const { return grp[perm[j]].count; }
+    __device__ double cov(int64_t j) const { return grp[perm[j]].coverage; }
+    __device__ double matched_cov(int64_t j, double) const { return grp[perm[j]].coverage; }     // the fold started from the resident value
+    __device__ double cov2(int64_t j) const { return grp[perm[j]].cov2; }
+    __device__ double conf(int64_t j) const { return grp[perm[j]].conf; }
+    __device__ double abd(int64_t j) const { return grp[perm[j]].abd; }
+    __device__ int32_t count1(int64_t j) const { return grp[perm[j]].count1; }
+    __device__ int64_t tid(int64_t j) const { const TxGroup &G = grp[perm[j]]; return ptid ? ptid[G.first] : tid_base + (((label ? label[G.graph] : (int64_t)G.graph) << 20) | (int64_t)G.path); }
+    __device__ int64_t sb(int64_t j) const { return sbeg[perm[j]]; }
+    __device__ int64_t se(int64_t j) const { return sbeg[perm[j] + 1]; }
+    __device__ void sample(int64_t s, int32_t &sid, double &c2, double &cf, double &ab, int32_t &c1) const { const TxSample &S = smp[s]; sid = S.sid; c2 = S.cov2; cf = S.conf; ab = S.abd; c1 = S.count1; }
+};
+struct InSet {                       // a second resident set (ald_tset_dev_merge)
+    SetView v; int64_t n;
+    __device__ uint64_t hash(int64_t j) const { return v.hash[j]; }
+    __device__ int nw(int64_t j) const { return (int)(2 * (v.eoff[j + 1] - v.eoff[j])); }
+    __device__ int strand(int64_t j) const { return (int)v.strand[j]; }
+    __device__ const int32_t *x(int64_t j) const { return v.lr + 2 * v.eoff[j]; }
+    __device__ int32_t lo(int64_t j) const { return x(j)[0]; }
+    __device__ int32_t hi(int64_t j) const { return x(j)[nw(j) - 1]; }
+    __device__ int32_t count(int64_t j) const { return v.count[j]; }
+    __device__ double cov(int64_t j) const { return v.cov[j]; }
+    __device__ double matched_cov(int64_t j, double c) const { return c + v.cov[j]; }          // trans_item::merge of two finished items
+    __device__ double cov2(int64_t j) const { return v.cov2[j]; }
+    __device__ double conf(int64_t j) const { return v.conf[j]; }
+    __device__ double abd(int64_t j) const { return v.abd[j]; }
+    __device__ int32_t count1(int64_t j) const { return v.count1[j]; }
+    __device__ int64_t tid(int64_t j) const { return v.tid[j]; }
+    __device__ int64_t sb(int64_t j) const { return v.soff[j]; }
+    __device__ int64_t se(int64_t j) const { return v.soff[j + 1]; }
+    __device__ void sample(int64_t s, int32_t &sid, double &c2, double &cf, double &ab, int32_t &c1) const { sid = v.ssid[s]; c2 = v.scov2[s]; cf = v.sconf[s]; ab = v.sabd[s]; c1 = v.sc1[s]; }
+};
+
+__device__ inline int64_t lane_id() { return (int64_t)blockIdx.x * TX_BLOCK + threadIdx.x; }
+
+// head position (in the sorted member order) of every group
+__global__ void rs_ghead(const int32_t *head, const int32_t *gid, int64_t n_dev, int32_t *ghead)
+{
+    const int64_t i = lane_id();
+    if(i < n_dev && head[i]) ghead[gid[i] - 1] = (int32_t)i;
+}
+// groups come out of the front end ordered by (bucket, 32-bit group hash); compare1 order inside a bucket: the first lane of every
+// equal-bucket run sorts the run (nearly always of length 1) by insertion
+__global__ void rs_order(TxIn in, const int64_t *sidx, const int32_t *ghead, const uint64_t *skey, int64_t n_groups, int32_t *perm)
+{
+    const int64_t k = lane_id();
+    if(k >= n_groups) return;
+    const uint64_t bk = skey[ghead[k]] >> 32;
+    if(k > 0 && (skey[ghead[k - 1]] >> 32) == bk) return;
+    int64_t e = k + 1; while(e < n_groups && (skey[ghead[e]] >> 32) == bk) e++;
+    for(int64_t q = k; q < e; q++) perm[q] = (int32_t)q;
+    for(int64_t q = k + 1; q < e; q++) {
+        const int32_t v = perm[q]; const uint32_t *rv = in.pool + in.roff[sidx[ghead[v]]];
+        int64_t p = q;
+        while(p > k) {
+            const uint32_t *ru = in.pool + in.roff[sidx[ghead[perm[p - 1]]]];
+            if(cmp1((int)rv[REC_NEXW], rec_strand(rv), rec_exons(rv), (int)ru[REC_NEXW], rec_strand(ru), rec_exons(ru)) != 1) break;
+            perm[p] = perm[p - 1]; p--;
+        }
+        perm[p] = v;
+    }
+}
+// match or insertion point of incoming item j in the resident set A; unm[j] = 1 for an item A does not have (unm[n] = 0 for the scan)
+template<class In> __global__ void rs_match(SetView A, In B, int64_t *match, int64_t *ins, int32_t *unm)
+{
+    const int64_t j = lane_id();
+    if(j > B.n) return;
+    if(j == B.n) { unm[j] = 0; return; }
+    const uint64_t h = B.hash(j);
+    int64_t lo = 0, hi = A.n;
+    while(lo < hi) { const int64_t m = (lo + hi) >> 1; if(A.hash[m] < h) lo = m + 1; else hi = m; }
+    const int nb = B.nw(j), sb = B.strand(j); const int32_t *xb = B.x(j);
+    int64_t p = lo; int c = 1;
+    while(p < A.n && A.hash[p] == h && (c = cmp1((int)(2 * (A.eoff[p + 1] - A.eoff[p])), (int)A.strand[p], A.lr + 2 * A.eoff[p], nb, sb, xb)) == 1) p++;
+    const bool hit = p < A.n && A.hash[p] == h && c == 0;
+    match[j] = hit ? p : -1; ins[j] = p; unm[j] = hit ? 0 : 1;
+}
+__global__ void rs_start(const int32_t *perm, const int64_t *match, int64_t n, int64_t *start_idx)
+{
+    const int64_t j = lane_id();
+    if(j < n) start_idx[perm[j]] = match[j];
+}
+// resident item -> the incoming item that lands on it; per resident position the number of new items placed in front of it
+__global__ void rs_mark(const int64_t *match, const int64_t *ins, int64_t n, int64_t *rmatch, int32_t *cnt)
+{
+    const int64_t j = lane_id();
+    if(j >= n) return;
+    if(match[j] >= 0) rmatch[match[j]] = j; else atomicAdd(&cnt[ins[j]], 1);
+}
+// output slot of every item: slot[o] = i (resident) or -(j + 1) (new); shift: inclusive scan of cnt, ub: exclusive scan of unm
+__global__ void rs_slots(int64_t nA, int64_t nB, const int32_t *shift, const int64_t *match, const int64_t *ins, const int32_t *ub, int64_t *slot)
+{
+    const int64_t t = lane_id();
+    if(t < nA) slot[t + shift[t]] = t;
+    else if(t < nA + nB) { const int64_t j = t - nA; if(match[j] < 0) slot[ins[j] + ub[j]] = -(j + 1); }
+}
+// the union of two ascending sid lists; emit(sid, from_a, ia, from_b, ib) once per distinct sid
+template<class In, class F> __device__ inline void sample_union(const SetView &A, int64_t i, const In &B, int64_t j, F emit)
+{
+    int64_t a = A.soff[i], ae = A.soff[i + 1], b = B.sb(j), be = B.se(j);
+    int32_t bs = 0, c1; double c2, cf, ab;
+    if(b < be) B.sample(b, bs, c2, cf, ab, c1);
+    while(a < ae || b < be) {
+        if(b >= be || (a < ae && A.ssid[a] < bs)) { emit(true, a, false, b); a++; }
+        else if(a >= ae || bs < A.ssid[a]) { emit(false, a, true, b); b++; if(b < be) B.sample(b, bs, c2, cf, ab, c1); }
+        else { emit(true, a, true, b); a++; b++; if(b < be) B.sample(b, bs, c2, cf, ab, c1); }
+    }
+}
+template<class In> __global__ void rs_sizes(SetView A, In B, const int64_t *slot, const int64_t *rmatch, int64_t N, int64_t *ecnt, int64_t *scnt)
+{
+    const int64_t o = lane_id();
+    if(o > N) return;
+    if(o == N) { ecnt[o] = 0; scnt[o] = 0; return; }
+    const int64_t s = slot[o];
+    if(s >= 0) {
+        const int64_t j = rmatch[s];
+        ecnt[o] = A.eoff[s + 1] - A.eoff[s];
+        if(j < 0) scnt[o] = A.soff[s + 1] - A.soff[s];
+        else { int64_t k = 0; sample_union(A, s, B, j, [&](bool, int64_t, bool, int64_t) { k++; }); scnt[o] = k; }
+    } else {
+        const int64_t j = -s - 1;
+        ecnt[o] = B.nw(j) / 2; scnt[o] = B.se(j) - B.sb(j);
+    }
+}
+// the gather: every output item from its resident item (+ the incoming item that lands on it) or from a new incoming item.  Maxima are
+// raised resident-first, as trans_item::merge raises the item that was there (transcript_set.cc:47-50, 63-66)
+template<class In> __global__ void rs_write(SetView A, In B, const int64_t *slot, const int64_t *rmatch, int64_t N, SetView O)
+{
+    const int64_t o = lane_id();
+    if(o >= N) return;
+    const int64_t s = slot[o];
+    int32_t *ox = O.lr + 2 * O.eoff[o]; int64_t so = O.soff[o];
+    if(s >= 0) {
+        const int64_t j = rmatch[s];
+        const int nw = (int)(2 * (A.eoff[s + 1] - A.eoff[s])); const int32_t *ax = A.lr + 2 * A.eoff[s];
+        for(int q = 0; q < nw; q++) ox[q] = ax[q];
+        O.hash[o] = A.hash[s]; O.strand[o] = A.strand[s]; O.tid[o] = A.tid[s];
+        int32_t cnt = A.count[s], c1 = A.count1[s]; double cov = A.cov[s], c2 = A.cov2[s], cf = A.conf[s], ab = A.abd[s];
+        if(j < 0) {
+            for(int64_t q = A.soff[s]; q < A.soff[s + 1]; q++, so++) { O.ssid[so] = A.ssid[q]; O.scov2[so] = A.scov2[q]; O.sconf[so] = A.sconf[q]; O.sabd[so] = A.sabd[q]; O.sc1[so] = A.sc1[q]; }
+        } else {
+            cnt += B.count(j); cov = B.matched_cov(j, cov);
+            if(c2 < B.cov2(j)) c2 = B.cov2(j); if(cf < B.conf(j)) cf = B.conf(j); if(ab < B.abd(j)) ab = B.abd(j); if(c1 < B.count1(j)) c1 = B.count1(j);
+            if(B.lo(j) < ox[0]) ox[0] = B.lo(j); if(B.hi(j) > ox[nw - 1]) ox[nw - 1] = B.hi(j);
+            sample_union(A, s, B, j, [&](bool ina, int64_t a, bool inb, int64_t b) {
+                int32_t sid, k1; double k2, kf, kb;
+                if(ina) { sid = A.ssid[a]; k2 = A.scov2[a]; kf = A.sconf[a]; kb = A.sabd[a]; k1 = A.sc1[a]; }
+                if(inb) {
+                    int32_t bs, b1; double b2, bf, bb; B.sample(b, bs, b2, bf, bb, b1);
+                    if(!ina) { sid = bs; k2 = b2; kf = bf; kb = bb; k1 = b1; }
+                    else { if(k2 < b2) k2 = b2; if(kf < bf) kf = bf; if(kb < bb) kb = bb; if(k1 < b1) k1 = b1; }
+                }
+                O.ssid[so] = sid; O.scov2[so] = k2; O.sconf[so] = kf; O.sabd[so] = kb; O.sc1[so] = k1; so++;
+            });
+        }
+        O.count[o] = cnt; O.cov[o] = cov; O.cov2[o] = c2; O.conf[o] = cf; O.abd[o] = ab; O.count1[o] = c1;
+    } else {
+        const int64_t j = -s - 1;
+        const int nw = B.nw(j); const int32_t *bx = B.x(j);
+        for(int q = 0; q < nw; q++) ox[q] = bx[q];
+        ox[0] = B.lo(j); ox[nw - 1] = B.hi(j);
+        O.hash[o] = B.hash(j); O.strand[o] = (int8_t)B.strand(j); O.tid[o] = B.tid(j);
+        O.count[o] = B.count(j); O.cov[o] = B.cov(j); O.cov2[o] = B.cov2(j); O.conf[o] = B.conf(j); O.abd[o] = B.abd(j); O.count1[o] = B.count1(j);
+        for(int64_t q = B.sb(j); q < B.se(j); q++, so++) {
+            int32_t sid, k1; double k2, kf, kb; B.sample(q, sid, k2, kf, kb, k1);
+            O.ssid[so] = sid; O.scov2[so] = k2; O.sconf[so] = kf; O.sabd[so] = kb; O.sc1[so] = k1;
+        }
+    }
+}
+// first sample run of every group (runs are sorted by group): sbeg[k] = lower bound of k in the runs' group ids
+__global__ void rs_sbeg(const TxSample *smp, int64_t n_runs, int64_t n_groups, int64_t *sbeg)
+{
+    const int64_t k = lane_id();
+    if(k > n_groups) return;
+    int64_t lo = 0, hi = n_runs;
+    while(lo < hi) { const int64_t m = (lo + hi) >> 1; if(smp[m].gid < k) lo = m + 1; else hi = m; }
+    sbeg[k] = lo;
+}
+
+} // namespace
+
+struct ald_tset_dev {
+    int device = 0; hipStream_t st = nullptr; hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    SetBufs buf[2]; int cur = 0;
+    aletsch::transcript_sink single;                        // transcripts with fewer than two exons, in call order
+    DevBuf red[20], d_pool, d_roff, d_label, d_tid; PinBuf pin[8];          // front end scratch (the set's own, never a batch's)
+    DevBuf w[16];                                           // merge-path scratch
+    double last_device_ms = 0, last_call_ms = 0;
+    explicit ald_tset_dev(double ov) : single(ov) {}
+    SetBufs &res() { return buf[cur]; }
+    const SetBufs &res() const { return buf[cur]; }
+    ~ald_tset_dev() {
+        for(auto &b : buf) b.release();
+        for(auto &d : red) d.release(); for(auto &d : w) d.release(); for(auto &p : pin) p.release();
+        d_pool.release(); d_roff.release(); d_label.release(); d_tid.release();
+        if(ev0) hipEventDestroy(ev0); if(ev1) hipEventDestroy(ev1);
+        if(st) hipStreamDestroy(st);
+    }
+};
+
+namespace {
+
+// The merge path: incoming items B (sorted, already matched against the resident set: match / ins / unm) into the other buffer set,
+// which becomes the resident one.  Nothing of the resident set changes before the swap.
+template<class In> int merge_path(ald_tset_dev *s, In B, const int64_t *match, const int64_t *ins, const int32_t *unm)
+{
+    hipStream_t st = s->st;
+    SetBufs &Ab = s->res(), &Ob = s->buf[s->cur ^ 1];
+    const SetView A = Ab.view(); const int64_t nA = Ab.n, nB = B.n;
+    DevBuf &d_ub = s->w[6], &d_cnt = s->w[7], &d_shift = s->w[8], &d_rmatch = s->w[9], &d_slot = s->w[10], &d_ecnt = s->w[11], &d_scnt = s->w[12], &d_tmp = s->w[15];
+    if(d_ub.ensure(4 * (size_t)(nB + 1)) || d_cnt.ensure(4 * (size_t)(nA + 1)) || d_shift.ensure(4 * (size_t)(nA + 1)) || d_rmatch.ensure(8 * (size_t)(nA + 1))) return ald_set_err(ALD_ERR_NOMEM, "resident set merge scratch");
+    size_t t1 = 0, t2 = 0;
+    HCHK(hipcub::DeviceScan::ExclusiveSum(nullptr, t1, (const int32_t*)unm, (int32_t*)d_ub.p, (int)(nB + 1), st));
+    HCHK(hipcub::DeviceScan::InclusiveSum(nullptr, t2, (const int32_t*)d_cnt.p, (int32_t*)d_shift.p, (int)(nA + 1), st));
+    if(d_tmp.ensure(std::max(t1, t2) + 256)) return ald_set_err(ALD_ERR_NOMEM, "resident set scan scratch");
+    HCHK(hipcub::DeviceScan::ExclusiveSum(d_tmp.p, t1, (const int32_t*)unm, (int32_t*)d_ub.p, (int)(nB + 1), st));
+    HCHK(hipMemsetAsync(d_cnt.p, 0, 4 * (size_t)(nA + 1), st));
+    HCHK(hipMemsetAsync(d_rmatch.p, 0xFF, 8 * (size_t)(nA + 1), st));
+    if(nB > 0) hipLaunchKernelGGL(rs_mark, dim3(grid_for(nB)), dim3(TX_BLOCK), 0, st, match, ins, nB, (int64_t*)d_rmatch.p, (int32_t*)d_cnt.p);
+    HCHK(hipcub::DeviceScan::InclusiveSum(d_tmp.p, t2, (const int32_t*)d_cnt.p, (int32_t*)d_shift.p, (int)(nA + 1), st));
+    PinBuf &p_cnt = s->pin[3];
+    if(p_cnt.ensure(64)) return ald_set_err(ALD_ERR_NOMEM, "pinned counter");
+    int64_t *hc = (int64_t*)p_cnt.p;
+    { int32_t *u = (int32_t*)(hc + 4); HCHK(hipMemcpyAsync(u, (const int32_t*)d_ub.p + nB, 4, hipMemcpyDeviceToHost, st)); HCHK(hipStreamSynchronize(st)); hc[0] = *u; }
+    const int64_t N = nA + hc[0];
+    if(d_slot.ensure(8 * (size_t)(N + 1)) || d_ecnt.ensure(8 * (size_t)(N + 1)) || d_scnt.ensure(8 * (size_t)(N + 1)) || Ob.ensure_items(N)) return ald_set_err(ALD_ERR_NOMEM, "resident set items");
+    if(N > 0) hipLaunchKernelGGL(rs_slots, dim3(grid_for(nA + nB)), dim3(TX_BLOCK), 0, st, nA, nB, (const int32_t*)d_shift.p, match, ins, (const int32_t*)d_ub.p, (int64_t*)d_slot.p);
+    hipLaunchKernelGGL(rs_sizes<In>, dim3(grid_for(N + 1)), dim3(TX_BLOCK), 0, st, A, B, (const int64_t*)d_slot.p, (const int64_t*)d_rmatch.p, N, (int64_t*)d_ecnt.p, (int64_t*)d_scnt.p);
+    size_t t3 = 0;
+    HCHK(hipcub::DeviceScan::ExclusiveSum(nullptr, t3, (const int64_t*)d_ecnt.p, (int64_t*)Ob.eoff.p, (int)(N + 1), st));
+    if(d_tmp.ensure(t3 + 256)) return ald_set_err(ALD_ERR_NOMEM, "resident set scan scratch");
+    HCHK(hipcub::DeviceScan::ExclusiveSum(d_tmp.p, t3, (const int64_t*)d_ecnt.p, (int64_t*)Ob.eoff.p, (int)(N + 1), st));
+    HCHK(hipcub::DeviceScan::ExclusiveSum(d_tmp.p, t3, (const int64_t*)d_scnt.p, (int64_t*)Ob.soff.p, (int)(N + 1), st));
+    HCHK(hipMemcpyAsync(hc + 1, (const int64_t*)Ob.eoff.p + N, 8, hipMemcpyDeviceToHost, st));
+    HCHK(hipMemcpyAsync(hc + 2, (const int64_t*)Ob.soff.p + N, 8, hipMemcpyDeviceToHost, st));
+    HCHK(hipStreamSynchronize(st));
+    const int64_t NE = hc[1], NS = hc[2];
+    if(Ob.ensure_tail(NE, NS)) return ald_set_err(ALD_ERR_NOMEM, "resident set exons / samples");
+    Ob.n = N; Ob.ne = NE; Ob.ns = NS;
+    const SetView O = Ob.view();
+    if(N > 0) hipLaunchKernelGGL(rs_write<In>, dim3(grid_for(N)), dim3(TX_BLOCK), 0, st, A, B, (const int64_t*)d_slot.p, (const int64_t*)d_rmatch.p, N, O);
+    if(s->ev1) HCHK(hipEventRecord(s->ev1, st));
+    HCHK(hipStreamSynchronize(st));
+    if(hipGetLastError() != hipSuccess) return ald_set_err(ALD_ERR_HIP, "a resident-set kernel failed");
+    s->cur ^= 1;
+    return ALD_OK;
+}
+
+// One batch (or stream) of records into the set.  d_pool / d_roff: records in (graph, path) order on the device; h_pool / h_roff / h_cov:
+// the same on the host (the single-exon part is merged there); label / h_tid as in tset_reduce.hip's reduce_core.
+int add_records(ald_tset_dev *s, const uint32_t *d_pool, const unsigned long long *d_roff, const uint32_t *h_pool, const unsigned long long *h_roff, const double *h_cov,
+                const int64_t *h_tid, int64_t np, int n_graphs, const int32_t *sid, const int64_t *label, int64_t tid_base, int32_t skip_single_exon)
+{
+    s->last_device_ms = 0;
+    if(np == 0) return ALD_OK;
+    hipStream_t st = s->st;
+    RedScratch S; S.red = s->red; S.pin = s->pin; S.st = st;
+    TxIn in; in.roff = d_roff; in.pool = d_pool; in.np = np;
+    TxFront X; X.ev0 = s->ev0;
+    { int rc = tx_front_groups(S, in, h_cov, n_graphs, sid, X); if(rc != ALD_OK) return rc; }
+    if(X.n_groups > 0) {
+        const int64_t G = X.n_groups;
+        DevBuf &d_ghead = s->w[0], &d_perm = s->w[1], &d_match = s->w[2], &d_ins = s->w[3], &d_unm = s->w[4], &d_start = s->w[5], &d_sbeg = s->w[13], &d_lab = s->d_label, &d_ptid = s->d_tid;
+        if(d_ghead.ensure(4 * (size_t)G) || d_perm.ensure(4 * (size_t)G) || d_match.ensure(8 * (size_t)G) || d_ins.ensure(8 * (size_t)G) || d_unm.ensure(4 * (size_t)(G + 1))
+           || d_start.ensure(8 * (size_t)G) || d_sbeg.ensure(8 * (size_t)(G + 1)) || (label && d_lab.ensure(8 * (size_t)n_graphs + 8)) || (h_tid && d_ptid.ensure(8 * (size_t)np + 8)))
+            return ald_set_err(ALD_ERR_NOMEM, "resident set batch scratch");
+        if(label) HCHK(hipMemcpyAsync(d_lab.p, label, 8 * (size_t)n_graphs, hipMemcpyHostToDevice, st));
+        if(h_tid) HCHK(hipMemcpyAsync(d_ptid.p, h_tid, 8 * (size_t)np, hipMemcpyHostToDevice, st));
+        hipLaunchKernelGGL(rs_ghead, dim3(grid_for(X.n_dev)), dim3(TX_BLOCK), 0, st, tx_head(S), tx_gid(S), X.n_dev, (int32_t*)d_ghead.p);
+        hipLaunchKernelGGL(rs_order, dim3(grid_for(G)), dim3(TX_BLOCK), 0, st, in, tx_sidx(S), (const int32_t*)d_ghead.p, tx_skey(S), G, (int32_t*)d_perm.p);
+        InBatch B; B.in = in; B.sidx = tx_sidx(S); B.ghead = (const int32_t*)d_ghead.p; B.skey = tx_skey(S); B.perm = (const int32_t*)d_perm.p;
+        B.grp = nullptr; B.smp = nullptr; B.sbeg = nullptr; B.tid_base = tid_base; B.label = label ? (const int64_t*)d_lab.p : nullptr; B.ptid = h_tid ? (const int64_t*)d_ptid.p : nullptr; B.n = G;
+        const SetView A = s->res().view();
+        hipLaunchKernelGGL(rs_match<InBatch>, dim3(grid_for(G + 1)), dim3(TX_BLOCK), 0, st, A, B, (int64_t*)d_match.p, (int64_t*)d_ins.p, (int32_t*)d_unm.p);
+        hipLaunchKernelGGL(rs_start, dim3(grid_for(G)), dim3(TX_BLOCK), 0, st, (const int32_t*)d_perm.p, (const int64_t*)d_match.p, G, (int64_t*)d_start.p);
+        { int rc = tx_front_fold(S, in, X, (const int64_t*)d_start.p, A.cov); if(rc != ALD_OK) return rc; }
+        hipLaunchKernelGGL(rs_sbeg, dim3(grid_for(G + 1)), dim3(TX_BLOCK), 0, st, (const TxSample*)tx_samples(S), (int64_t)X.n_runs, G, (int64_t*)d_sbeg.p);
+        B.grp = tx_groups(S); B.smp = tx_samples(S); B.sbeg = (const int64_t*)d_sbeg.p;
+        { int rc = merge_path(s, B, (const int64_t*)d_match.p, (const int64_t*)d_ins.p, (const int32_t*)d_unm.p); if(rc != ALD_OK) return rc; }
+    } else {
+        HCHK(hipEventRecord(s->ev1, st));
+        HCHK(hipStreamSynchronize(st));
+    }
+    float ms = 0; if(hipEventElapsedTime(&ms, s->ev0, s->ev1) == hipSuccess) s->last_device_ms = ms;
+    // the device part is in: the transcripts with fewer than two exons, graph by graph, into the host part
+    if(!skip_single_exon) tx_host_singles(s->single, X.host_paths, h_pool, h_roff, h_cov, h_tid, sid, label, tid_base);
+    return ALD_OK;
+}
+
+int has_device(int32_t device)
+{
+    int ndev = 0;
+    if(hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return ald_set_err(ALD_ERR_NO_DEVICE, "no HIP device visible: the resident transcript set has no CPU fallback");
+    if(device < 0 || device >= ndev) return ald_set_err(ALD_ERR_INVALID, "device index out of range");
+    return ALD_OK;
+}
+
+// The device part, copied back: flat arrays in the set's order (exon / sample offsets included), count2 = #samples
+int fetch_device_part(const ald_tset_dev *cs, ald_tset_flat &D)
+{
+    ald_tset_dev *s = const_cast<ald_tset_dev*>(cs);
+    const SetBufs &R = s->res(); const int64_t n = R.n, ne = R.ne, ns = R.ns;
+    hipStream_t st = s->st;
+    D.hash.resize((size_t)n); D.count.resize((size_t)n); D.strand.resize((size_t)n); D.coverage.resize((size_t)n); D.cov2.resize((size_t)n); D.conf.resize((size_t)n); D.abd.resize((size_t)n);
+    D.count1.resize((size_t)n); D.count2.resize((size_t)n); D.tid.resize((size_t)n); D.exon_offset.assign((size_t)n + 1, 0); D.sample_offset.assign((size_t)n + 1, 0);
+    D.exon_lr.resize(2 * (size_t)ne); D.sample_sid.resize((size_t)ns); D.sample_count1.resize((size_t)ns); D.sample_cov2.resize((size_t)ns); D.sample_conf.resize((size_t)ns); D.sample_abd.resize((size_t)ns);
+    if(n == 0) return ALD_OK;
+    auto get = [&](void *dst, const DevBuf &src, size_t bytes) { return bytes ? hipMemcpyAsync(dst, src.p, bytes, hipMemcpyDeviceToHost, st) : hipSuccess; };
+    HCHK(get(D.hash.data(), R.hash, 8 * (size_t)n)); HCHK(get(D.count.data(), R.count, 4 * (size_t)n)); HCHK(get(D.strand.data(), R.strand, (size_t)n));
+    HCHK(get(D.coverage.data(), R.cov, 8 * (size_t)n)); HCHK(get(D.cov2.data(), R.cov2, 8 * (size_t)n)); HCHK(get(D.conf.data(), R.conf, 8 * (size_t)n)); HCHK(get(D.abd.data(), R.abd, 8 * (size_t)n));
+    HCHK(get(D.count1.data(), R.count1, 4 * (size_t)n)); HCHK(get(D.tid.data(), R.tid, 8 * (size_t)n));
+    HCHK(get(D.exon_offset.data(), R.eoff, 8 * ((size_t)n + 1))); HCHK(get(D.sample_offset.data(), R.soff, 8 * ((size_t)n + 1)));
+    HCHK(get(D.exon_lr.data(), R.lr, 8 * (size_t)ne)); HCHK(get(D.sample_sid.data(), R.ssid, 4 * (size_t)ns)); HCHK(get(D.sample_count1.data(), R.sc1, 4 * (size_t)ns));
+    HCHK(get(D.sample_cov2.data(), R.scov2, 8 * (size_t)ns)); HCHK(get(D.sample_conf.data(), R.sconf, 8 * (size_t)ns)); HCHK(get(D.sample_abd.data(), R.sabd, 8 * (size_t)ns));
+    HCHK(hipStreamSynchronize(st));
+    for(int64_t i = 0; i < n; i++) D.count2[(size_t)i] = (int32_t)(D.sample_offset[(size_t)i + 1] - D.sample_offset[(size_t)i]);
+    return ALD_OK;
+}
+
+// item i of flat set `S` appended to F (offsets of F kept as running totals in F.exon_offset / F.sample_offset's last entry)
+void append_item(ald_tset_flat &F, const ald_tset_flat &S, size_t i)
+{
+    F.hash.push_back(S.hash[i]); F.count.push_back(S.count[i]); F.strand.push_back(S.strand[i]); F.coverage.push_back(S.coverage[i]); F.cov2.push_back(S.cov2[i]);
+    F.conf.push_back(S.conf[i]); F.abd.push_back(S.abd[i]); F.count1.push_back(S.count1[i]); F.count2.push_back(S.count2[i]); F.tid.push_back(S.tid[i]);
+    F.exon_lr.insert(F.exon_lr.end(), S.exon_lr.begin() + 2 * S.exon_offset[i], S.exon_lr.begin() + 2 * S.exon_offset[i + 1]);
+    F.exon_offset.push_back(F.exon_offset.back() + S.exon_offset[i + 1] - S.exon_offset[i]);
+    for(int64_t q = S.sample_offset[i]; q < S.sample_offset[i + 1]; q++) {
+        F.sample_sid.push_back(S.sample_sid[(size_t)q]); F.sample_cov2.push_back(S.sample_cov2[(size_t)q]); F.sample_conf.push_back(S.sample_conf[(size_t)q]);
+        F.sample_abd.push_back(S.sample_abd[(size_t)q]); F.sample_count1.push_back(S.sample_count1[(size_t)q]);
+    }
+    F.sample_offset.push_back(F.sample_offset.back() + S.sample_offset[i + 1] - S.sample_offset[i]);
+}
+
+// the whole set, flat, in the reference's iteration order: the host items (fewer than two exons) spliced in by hash, ahead of the device
+// items of the same hash (compare1 puts fewer exons first, transcript.cc:271)
+int snapshot(const ald_tset_dev *s, ald_tset_flat &F)
+{
+    ald_tset_flat D, H;
+    { int rc = fetch_device_part(s, D); if(rc != ALD_OK) return rc; }
+    H.exon_offset.push_back(0); H.sample_offset.push_back(0);
+    for(size_t key : s->single.sorted_keys()) for(auto &z : s->single.mt.find(key)->second) {
+        const aletsch::sink_transcript &r = z.trst;
+        H.hash.push_back(key); H.count.push_back(z.count); H.strand.push_back(r.strand); H.coverage.push_back(r.coverage); H.cov2.push_back(r.top.cov2); H.conf.push_back(r.top.conf);
+        H.abd.push_back(r.top.abd); H.count1.push_back(r.top.count1); H.count2.push_back(r.count2); H.tid.push_back(r.tid);
+        H.exon_lr.insert(H.exon_lr.end(), r.xs.begin(), r.xs.end()); H.exon_offset.push_back(H.exon_offset.back() + (int64_t)r.n_exons());
+        for(auto &q : z.samples) { H.sample_sid.push_back(q.first); H.sample_cov2.push_back(q.second.top.cov2); H.sample_conf.push_back(q.second.top.conf); H.sample_abd.push_back(q.second.top.abd); H.sample_count1.push_back(q.second.top.count1); }
+        H.sample_offset.push_back(H.sample_offset.back() + (int64_t)z.samples.size());
+    }
+    const size_t NG = D.hash.size(), NH = H.hash.size();
+    if(NH == 0) F = std::move(D);
+    else {
+        F.exon_offset.push_back(0); F.sample_offset.push_back(0);
+        for(size_t h = 0, i = 0; h < NH || i < NG; ) {
+            if(h < NH && (i >= NG || H.hash[h] <= D.hash[i])) append_item(F, H, h++);
+            else append_item(F, D, i++);
+        }
+    }
+    F.n_device_groups = (int64_t)NG; F.n_host_items = (int64_t)NH;
+    return ALD_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+int ald_tset_dev_create(int32_t device, double single_exon_overlap, ald_tset_dev **out)
+{
+    if(!out) return ALD_ERR_INVALID;
+    *out = nullptr;
+    { int rc = has_device(device); if(rc != ALD_OK) return rc; }
+    HCHK(hipSetDevice(device));
+    std::unique_ptr<ald_tset_dev> s(new ald_tset_dev(single_exon_overlap));
+    s->device = device;
+    HCHK(hipStreamCreateWithFlags(&s->st, hipStreamNonBlocking));
+    HCHK(hipEventCreate(&s->ev0)); HCHK(hipEventCreate(&s->ev1));
+    *out = s.release();
+    return ALD_OK;
+}
+
+int ald_tset_dev_destroy(ald_tset_dev *s)
+{
+    if(!s) return ALD_OK;
+    hipSetDevice(s->device);
+    if(s->st) hipStreamSynchronize(s->st);
+    delete s;
+    return ALD_OK;
+}
+
+int ald_tset_dev_add_batch(ald_tset_dev *s, const ald_batch *cb, const int32_t *sid, int64_t tid_base, int32_t skip_single_exon)
+{
+    if(!s || !cb) return ALD_ERR_INVALID;
+    if(cb->device != s->device) return ald_set_err(ALD_ERR_INVALID, "ald_tset_dev_add_batch: the batch lives on another device");
+    if(!cb->downloaded) return ald_set_err(ALD_ERR_STATE, "ald_tset_dev_add_batch before ald_batch_download");
+    const auto T0 = std::chrono::steady_clock::now();
+    ald_batch *b = const_cast<ald_batch*>(cb);
+    HCHK(hipSetDevice(s->device));
+    { int rc = device_path_table(b); if(rc != ALD_OK) return rc; }
+    HCHK(hipStreamSynchronize(b->stream));                 // the path table is built on the batch's stream; everything else runs on the set's
+    const int rc = add_records(s, (const uint32_t*)b->d_pool.p, (const unsigned long long*)b->d_ordoff.p, b->res.pool_data(), (const unsigned long long*)b->res.rec_off.data(),
+                               b->res.coverage.data(), nullptr, b->total_paths, b->hb.n(), sid, nullptr, tid_base, skip_single_exon);
+    s->last_call_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - T0).count();
+    return rc;
+}
+
+int ald_tset_dev_add_stream(ald_tset_dev *s, const uint32_t *words, int64_t n_words, const double *coverage, const int64_t *tid, int32_t graph_offset, int64_t tid_base, int32_t skip_single_exon)
+{
+    if(!s || n_words < 0 || (n_words > 0 && !words)) return ALD_ERR_INVALID;
+    const auto T0 = std::chrono::steady_clock::now();
+    HCHK(hipSetDevice(s->device));
+    std::vector<uint32_t> staged;                           // a stream in device memory (e.g. one an RCCL gather left there) comes to the host first
+    hipPointerAttribute_t at;
+    if(n_words > 0 && hipPointerGetAttributes(&at, words) == hipSuccess && at.type == hipMemoryTypeDevice) {
+        staged.resize((size_t)n_words);
+        HCHK(hipMemcpy(staged.data(), words, 4 * (size_t)n_words, hipMemcpyDeviceToHost));
+        words = staged.data();
+    }
+    hipGetLastError();                                      // (a host pointer unknown to the runtime leaves an error behind)
+    StreamRecords R;
+    { int rc = tx_stream_records(words, n_words, coverage, tid, skip_single_exon, graph_offset, R); if(rc != ALD_OK) return rc; }
+    const int64_t np = (int64_t)R.roff.size();
+    if(np > 0) {
+        if(s->d_pool.ensure(4 * R.pool.size() + 64) || s->d_roff.ensure(8 * (size_t)np + 8)) return ald_set_err(ALD_ERR_NOMEM, "resident set stream buffers");
+        HCHK(hipMemcpyAsync(s->d_pool.p, R.pool.data(), 4 * R.pool.size(), hipMemcpyHostToDevice, s->st));
+        HCHK(hipMemcpyAsync(s->d_roff.p, R.roff.data(), 8 * (size_t)np, hipMemcpyHostToDevice, s->st));
+    }
+    const int rc = add_records(s, (const uint32_t*)s->d_pool.p, (const unsigned long long*)s->d_roff.p, R.pool.data(), R.roff.data(), R.cov.data(), tid ? R.tids.data() : nullptr,
+                               np, (int)R.label.size(), R.sid.empty() ? nullptr : R.sid.data(), R.label.data(), tid_base, 0 /* filtered above */);
+    s->last_call_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - T0).count();
+    return rc;
+}
+
+int ald_tset_dev_merge(ald_tset_dev *dst, ald_tset_dev *src)
+{
+    if(!dst || !src || dst == src) return ALD_ERR_INVALID;
+    if(dst->device != src->device) return ald_set_err(ALD_ERR_INVALID, "ald_tset_dev_merge: the sets live on different devices");
+    const auto T0 = std::chrono::steady_clock::now();
+    HCHK(hipSetDevice(dst->device));
+    HCHK(hipStreamSynchronize(src->st));
+    SetBufs &Sb = src->res(); const int64_t nB = Sb.n;
+    dst->last_device_ms = 0;
+    if(nB > 0) {
+        hipStream_t st = dst->st;
+        DevBuf &d_match = dst->w[2], &d_ins = dst->w[3], &d_unm = dst->w[4];
+        if(d_match.ensure(8 * (size_t)nB) || d_ins.ensure(8 * (size_t)nB) || d_unm.ensure(4 * (size_t)(nB + 1))) return ald_set_err(ALD_ERR_NOMEM, "resident set merge scratch");
+        HCHK(hipEventRecord(dst->ev0, st));
+        InSet B; B.v = Sb.view(); B.n = nB;
+        hipLaunchKernelGGL(rs_match<InSet>, dim3(grid_for(nB + 1)), dim3(TX_BLOCK), 0, st, dst->res().view(), B, (int64_t*)d_match.p, (int64_t*)d_ins.p, (int32_t*)d_unm.p);
+        { int rc = merge_path(dst, B, (const int64_t*)d_match.p, (const int64_t*)d_ins.p, (const int32_t*)d_unm.p); if(rc != ALD_OK) return rc; }
+        float ms = 0; if(hipEventElapsedTime(&ms, dst->ev0, dst->ev1) == hipSuccess) dst->last_device_ms = ms;
+    }
+    dst->single.add(src->single);                           // transcript_set::add(transcript_set&) for the host part
+    src->single.clear(); Sb.n = Sb.ne = Sb.ns = 0;
+    dst->last_call_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - T0).count();
+    return ALD_OK;
+}
+
+int ald_tset_dev_size(const ald_tset_dev *s, int64_t *n_items, int64_t *n_exons, int64_t *n_samples)
+{
+    if(!s) return ALD_ERR_INVALID;
+    int64_t a = s->res().n, e = s->res().ne, m = s->res().ns;
+    for(auto &x : s->single.mt) for(auto &z : x.second) { a++; e += (int64_t)z.trst.n_exons(); m += (int64_t)z.samples.size(); }
+    if(n_items) *n_items = a; if(n_exons) *n_exons = e; if(n_samples) *n_samples = m;
+    return ALD_OK;
+}
+
+int ald_tset_dev_snapshot(const ald_tset_dev *s, ald_tset_flat **out)
+{
+    if(!s || !out) return ALD_ERR_INVALID;
+    const auto T0 = std::chrono::steady_clock::now();
+    HCHK(hipSetDevice(s->device));
+    std::unique_ptr<ald_tset_flat> F(new ald_tset_flat());
+    { int rc = snapshot(s, *F); if(rc != ALD_OK) return rc; }
+    F->host_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - T0).count();
+    *out = F.release();
+    return ALD_OK;
+}
+
+int ald_tset_dev_export(const ald_tset_dev *s, uint64_t *hash, int32_t *count, char *strand, double *coverage, double *cov2, double *conf, double *abd,
+                        int32_t *count1, int32_t *count2, int64_t *tid, int64_t *exon_offset, int32_t *exon_lr,
+                        int64_t *sample_offset, int32_t *sample_sid, double *sample_cov2, double *sample_conf, double *sample_abd, int32_t *sample_count1)
+{
+    if(!s) return ALD_ERR_INVALID;
+    ald_tset_flat *F = nullptr;
+    { int rc = ald_tset_dev_snapshot(s, &F); if(rc != ALD_OK) return rc; }
+    const int rc = ald_tset_flat_export(F, hash, count, strand, coverage, cov2, conf, abd, count1, count2, tid, exon_offset, exon_lr, sample_offset, sample_sid, sample_cov2, sample_conf, sample_abd, sample_count1);
+    ald_tset_flat_free(F);
+    return rc;
+}
+
+int ald_tset_dev_stats(const ald_tset_dev *s, double *last_device_ms, double *last_call_ms, int64_t *device_items, int64_t *host_items)
+{
+    if(!s) return ALD_ERR_INVALID;
+    if(last_device_ms) *last_device_ms = s->last_device_ms; if(last_call_ms) *last_call_ms = s->last_call_ms;
+    if(device_items) *device_items = s->res().n;
+    if(host_items) *host_items = (int64_t)s->single.size();
+    return ALD_OK;
+}
+
+} // extern "C"

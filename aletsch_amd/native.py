@@ -223,6 +223,15 @@ def load_library():
     lib.ald_tset_add_flat.argtypes = [C.c_void_p, C.c_void_p]
     lib.ald_tset_merge.argtypes = [C.c_void_p, C.c_void_p]
     lib.ald_tset_flat_free.argtypes = [C.c_void_p]
+    lib.ald_tset_dev_create.argtypes = [C.c_int32, C.c_double, C.POINTER(C.c_void_p)]
+    lib.ald_tset_dev_destroy.argtypes = [C.c_void_p]
+    lib.ald_tset_dev_add_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32]
+    lib.ald_tset_dev_add_stream.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int32]
+    lib.ald_tset_dev_merge.argtypes = [C.c_void_p, C.c_void_p]
+    lib.ald_tset_dev_size.argtypes = [C.c_void_p] + [C.POINTER(C.c_int64)] * 3
+    lib.ald_tset_dev_export.argtypes = [C.c_void_p] * 19
+    lib.ald_tset_dev_snapshot.argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]
+    lib.ald_tset_dev_stats.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     _LIB = lib
     return lib
 
@@ -537,6 +546,77 @@ class TranscriptSink:
     def items(self):
         """List of dicts in the reference's iteration order (bucket hash ascending, then bucket order)."""
         return _export_items(lambda *a: self._lib.ald_tset_size(self._h, *a), lambda *a: self._lib.ald_tset_export(self._h, *a))
+
+
+class DeviceTranscriptSet:
+    """A transcript set that lives in HBM (ald_tset_dev_*): batches and transcript streams fold into it on the GPU with the reference's
+    merge semantics (meta/assembler.cc:1105-1133, rnacore/transcript_set.cc:38-175); items() / snapshot_into() bring it back."""
+
+    def __init__(self, device: int = 0, single_exon_overlap: float = 0.8):
+        self._lib = load_library(); self._h = C.c_void_p()
+        _check(self._lib.ald_tset_dev_create(C.c_int32(device), C.c_double(single_exon_overlap), C.byref(self._h)))
+
+    def close(self):
+        if self._h:
+            self._lib.ald_tset_dev_destroy(self._h); self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def add_batch(self, batch: "DecompBatch", sid=None, tid_base: int = 0, skip_single_exon: bool = False):
+        """Every transcript of a downloaded batch, graph by graph (== TranscriptSink.add_batch); the batch may be reused on return."""
+        sp = None
+        if sid is not None:
+            sid = np.ascontiguousarray(sid, np.int32); assert len(sid) == batch.n; sp = C.c_void_p(sid.ctypes.data)
+        _check(self._lib.ald_tset_dev_add_batch(self._h, batch._h, sp, C.c_int64(tid_base), C.c_int32(int(skip_single_exon))))
+
+    def add_stream(self, words: np.ndarray, coverage=None, tid=None, graph_offset: int = 0, tid_base: int = 0, skip_single_exon: bool = False):
+        """A transcript stream graph by graph; coverage / tid: optional, one per transcript of the stream (as reduce_stream)."""
+        words = np.ascontiguousarray(words, np.uint32)
+        cp = tp = None
+        if coverage is not None:
+            coverage = np.ascontiguousarray(coverage, np.float64); cp = C.c_void_p(coverage.ctypes.data)
+        if tid is not None:
+            tid = np.ascontiguousarray(tid, np.int64); tp = C.c_void_p(tid.ctypes.data)
+        _check(self._lib.ald_tset_dev_add_stream(self._h, C.c_void_p(words.ctypes.data), C.c_int64(words.size), cp, tp, C.c_int32(int(graph_offset)),
+                                                 C.c_int64(int(tid_base)), C.c_int32(int(skip_single_exon))))
+
+    def merge(self, other: "DeviceTranscriptSet"):
+        """transcript_set::add(transcript_set&) on the device; `other` is left empty."""
+        _check(self._lib.ald_tset_dev_merge(self._h, other._h))
+
+    def size(self):
+        """(items, exons, samples)"""
+        v = [C.c_int64() for _ in range(3)]
+        _check(self._lib.ald_tset_dev_size(self._h, *[C.byref(x) for x in v]))
+        return tuple(x.value for x in v)
+
+    def items(self):
+        """List of dicts in TranscriptSink.items() form and order."""
+        return _export_items(lambda *a: self._lib.ald_tset_dev_size(self._h, *a), lambda *a: self._lib.ald_tset_dev_export(self._h, *a))
+
+    def snapshot_into(self, sink: "TranscriptSink"):
+        """The set, flat (ald_tset_dev_snapshot), merged into a host sink (ald_tset_add_flat)."""
+        h = C.c_void_p()
+        _check(self._lib.ald_tset_dev_snapshot(self._h, C.byref(h)))
+        try:
+            _check(self._lib.ald_tset_add_flat(sink._h, h))
+        finally:
+            self._lib.ald_tset_flat_free(h)
+
+    def stats(self):
+        st = [C.c_double(), C.c_double(), C.c_int64(), C.c_int64()]
+        _check(self._lib.ald_tset_dev_stats(self._h, *[C.byref(x) for x in st]))
+        return dict(device_ms=st[0].value, call_ms=st[1].value, device_items=st[2].value, host_items=st[3].value)
 
 
 def reduce_stream(words: np.ndarray, coverage=None, tid=None, tid_base: int = 0, skip_single_exon: bool = False, single_exon_overlap: float = 0.8, device: int = 0):

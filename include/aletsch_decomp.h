@@ -331,6 +331,37 @@ int  ald_tset_flat_stats(const ald_tset_flat *f, double *device_ms, double *tota
 int  ald_tset_add_flat(ald_tset *t, const ald_tset_flat *f);
 int  ald_tset_flat_free(ald_tset_flat *f);
 
+/* ---- a transcript set that lives in HBM (the region's `tm` of meta/assembler.cc:1105-1133 kept on the device) ----
+ * Batches and transcript streams fold into it on the GPU, call after call, with the reference's exact sequence of floating-point
+ * additions: a group that lands on a resident item of coverage c sums ((c + s1) + s2) + ..., s_k being graph k's own left-to-right sum
+ * (transcript_set.cc:38-81, 149-175).  Items are kept sorted by (bucket hash, compare1); transcripts with fewer than two exons (their
+ * overlap rule is not transitive) stay in a host part inside the set, fed graph by graph in call order, and are spliced in by hash on
+ * export.  The set owns its stream and scratch; one set is not thread-safe, two sets on two threads are.  Without a HIP device
+ * ald_tset_dev_create returns ALD_ERR_NO_DEVICE.
+ *   add_batch    == ald_tset_add_batch on a host set fed the same sequence.  Needs a DOWNLOADED batch (ALD_ERR_STATE otherwise) on the
+ *                   set's device (ALD_ERR_INVALID otherwise); returns when the batch is no longer read: it may be cleared and reused.
+ *   add_stream   == ald_tset_add_stream (stream format of ald_batch_transcript_stream; words in host or device memory).  coverage[i] /
+ *                   tid[i] (optional, one per transcript of the stream): as ald_tset_reduce_stream; NULL: log(1 + weight) and
+ *                   tid_base + ((graph + graph_offset) << 20 | path index).  Unlike ald_tset_add_stream it takes skip_single_exon.
+ *   merge        == ald_tset_merge (transcript_set::add(transcript_set&)): c_dst + c_src; src is left empty.
+ *   size / export / snapshot   the items in the reference's iteration order (the arrays of ald_tset_export; snapshot: an ald_tset_flat
+ *                   for ald_tset_flat_export / ald_tset_add_flat).
+ *   stats        device milliseconds (HIP events) and wall milliseconds of the last add / merge, items on the device, items on the host.
+ * ALD_ERR_NOMEM on growth leaves the set as it was. */
+typedef struct ald_tset_dev ald_tset_dev;
+int  ald_tset_dev_create(int32_t device, double single_exon_overlap, ald_tset_dev **out);
+int  ald_tset_dev_destroy(ald_tset_dev *s);
+int  ald_tset_dev_add_batch(ald_tset_dev *s, const ald_batch *b, const int32_t *sid /* [graphs] or NULL => -1 */, int64_t tid_base, int32_t skip_single_exon);
+int  ald_tset_dev_add_stream(ald_tset_dev *s, const uint32_t *words, int64_t n_words, const double *coverage, const int64_t *tid,
+                             int32_t graph_offset, int64_t tid_base, int32_t skip_single_exon);
+int  ald_tset_dev_merge(ald_tset_dev *dst, ald_tset_dev *src);
+int  ald_tset_dev_size(const ald_tset_dev *s, int64_t *n_items, int64_t *n_exons, int64_t *n_samples);
+int  ald_tset_dev_export(const ald_tset_dev *s, uint64_t *hash, int32_t *count, char *strand, double *coverage, double *cov2, double *conf, double *abd,
+                         int32_t *count1, int32_t *count2, int64_t *tid, int64_t *exon_offset, int32_t *exon_lr,
+                         int64_t *sample_offset, int32_t *sample_sid, double *sample_cov2, double *sample_conf, double *sample_abd, int32_t *sample_count1);
+int  ald_tset_dev_snapshot(const ald_tset_dev *s, ald_tset_flat **out);
+int  ald_tset_dev_stats(const ald_tset_dev *s, double *last_device_ms, double *last_call_ms, int64_t *device_items, int64_t *host_items);
+
 /* ---- the exchange step for a multi-PROCESS host (one process per MI355X): transcript streams -> rank 0 over RCCL / xGMI ----
  * (A host that drives all its devices from one process -- aletsch::gpu_assembly_queue over a device list -- needs none of this.)
  * RCCL is loaded on first use.  Bootstrap: rank 0 calls ald_comm_unique_id and ships the 128 bytes to the other ranks by its own
