@@ -320,6 +320,7 @@ int ald_batch_destroy(ald_batch *b)
     for(DevBuf &d : b->red) d.release();
     for(DevBuf &d : b->dts) d.release();
     for(PinBuf &d : b->red_pin) d.release();
+    b->feat.release();
     for(int q = 0; q < ALD_SIDE_STREAMS_MAX; q++) if(b->cstream[q]) { hipStreamSynchronize(b->cstream[q]); hipStreamDestroy(b->cstream[q]); }
     for(int c = 0; c < ALD_NUM_SLOTS; c++) if(b->cdone[c]) hipEventDestroy(b->cdone[c]);
     if(b->ev0) hipEventDestroy(b->ev0);
@@ -334,7 +335,7 @@ int ald_batch_destroy(ald_batch *b)
 int ald_batch_clear(ald_batch *b)
 {
     if(!b) return ALD_ERR_INVALID;
-    b->hb.clear(); b->res.clear(); b->uploaded = b->ran = b->downloaded = false; b->kernel_ms = -1;
+    b->hb.clear(); b->res.clear(); b->uploaded = b->ran = b->downloaded = false; b->kernel_ms = -1; b->feat.valid = false;
     return ALD_OK;
 }
 
@@ -545,6 +546,7 @@ int ald_batch_download(ald_batch *b)
     if(!b->ran) return set_err(ALD_ERR_STATE, "ald_batch_download before ald_batch_run");
     HIPCHK(hipSetDevice(b->device));
     const int n = b->hb.n();
+    b->feat.valid = false;
     const bool prof = getenv("ALD_DOWNLOAD_PROF") != nullptr; const auto P0 = std::chrono::steady_clock::now(); auto P1 = P0, P2 = P0, P3 = P0;
     b->n_paths.assign(n, 0); b->n_iters.assign(n, 0);
     // Everything comes back through async copies on the batch's OWN stream into pinned memory.  (A synchronous hipMemcpy runs on the

@@ -34,6 +34,17 @@ struct StagedPass {
     int nblk[ALD_NUM_SLOTS]; int order[ALD_NUM_SLOTS]; int stream_of[ALD_NUM_SLOTS]; int nord = 0; size_t tot = 0;
 };
 
+// the feature table of the last ald_batch_features_all (trst_features.hip): host rows in pinned memory, valid until the next download / clear
+struct FeatTable {
+    DevBuf d_rows, d_complete, d_rc, d_scratch, d_x[10];
+    PinBuf h_rows, h_complete, h_rc;
+    std::vector<int64_t> row_begin;
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    bool valid = false; double device_ms = 0, call_ms = 0; int64_t device_graphs = 0, host_graphs = 0, n_rows = 0;
+    void release() { DevBuf *d[] = {&d_rows, &d_complete, &d_rc, &d_scratch}; for(DevBuf *x : d) x->release(); for(DevBuf &x : d_x) x.release();
+                     h_rows.release(); h_complete.release(); h_rc.release(); if(e0) hipEventDestroy(e0); if(e1) hipEventDestroy(e1); e0 = e1 = nullptr; valid = false; }
+};
+
 struct ald_batch {
     int device = 0; int n_cus = 0;
     Params prm;
@@ -73,6 +84,7 @@ struct ald_batch {
     rvec<uint32_t> tstream;                                // last transcript stream built from this batch (ald_batch_transcript_stream)
     DevBuf red[20]; PinBuf red_pin[8];                     // scratch of ald_batch_reduce_transcripts, kept across calls (tset_reduce.hip)
     DevBuf dts[3];                                         // ald_batch_device_transcript_stream: lengths / offsets / the stream itself
+    FeatTable feat;                                        // ald_batch_features_all
 };
 
 

@@ -204,11 +204,95 @@ public:
         for(int k = 0; k < r.num_paths; k++) { ald_path_view pv; ald_batch_get_path(b_, i, k, &pv); out.push_back(make_path<Path>(pv, lpos_[i], rpos_[i])); }
         return out;
     }
-    void clear() { ald_batch_clear(b_); lpos_.clear(); rpos_.clear(); }
+    void clear() { ald_batch_clear(b_); lpos_.clear(); rpos_.clear(); extras_.clear(); }
     ald_batch *handle() const { return b_; }        // for the calls that take the batch itself (ald_tset_add_batch, ald_batch_export_transcripts, ...)
+
+    // ---- the transcript feature block (scallop::update_trst_features, scallop.cc:3268-3451), opt-in.  Member templates: instantiated only
+    // where they are used, so graph types without the feature members (vertex_info's boundary / unbridged fields, splice_graph::reads /
+    // subgraph) still work with everything above.
+    // enqueue() / enqueue_raw() that also record what the features read beyond the decomposition's inputs, from the graph's own objects
+    // (rnacore/vertex_info.h:34-41, splice_graph.h:36-37).  A graph enqueued without them reads zeros there.
+    template<class G>
+    int enqueue_with_extras(G &gr, const HyperSet &hs) { const int t = enqueue(gr, hs); record_extras(t, gr); return t; }
+    template<class G, class PhaseSet>
+    int enqueue_raw_with_extras(G &gx, const PhaseSet &px, int max_group_boundary_distance = 10000) { const int t = enqueue_raw(gx, px, max_group_boundary_distance); record_extras(t, gx); return t; }
+    // After flush(): the features of every path of ticket i, in path order, in a caller type F with the field names of the reference's
+    // transcript::TrstFeatures (gtf/transcript.h:60-104) -- what build_transcripts puts into trst.features before ts.add.  The whole batch
+    // is computed by the first call after a flush (ald_batch_features_all: one device pass; raw graphs by the host routine).  `status`
+    // receives what the reference's asserts would have said (ALD_OK, or ALD_ST_INVARIANT + ALD_INV_OTHER); `complete` (optional): 0 for
+    // a path without a junction, whose fields past the first seven the reference never sets.
+    template<class F>
+    std::vector<F> features(int i, int *status = nullptr, std::vector<int> *complete = nullptr) {
+        const ald_trst_features *rows = nullptr; const int32_t *comp = nullptr, *rc = nullptr; const int64_t *rb = nullptr; int64_t nr = 0;
+        if(ald_batch_features_table(b_, &rows, &comp, &rc, &rb, &nr) != ALD_OK) {
+            compute_features();
+            int r = ald_batch_features_table(b_, &rows, &comp, &rc, &rb, &nr);
+            if(r != ALD_OK) throw gpu_error(r, "ald_batch_features_table");
+        }
+        if(i < 0 || i >= (int)lpos_.size()) throw gpu_error(ALD_ERR_INVALID, "features: no such ticket");
+        std::vector<F> out;
+        if(status) *status = rc[i];
+        if(complete) complete->clear();
+        for(int64_t k = rb[i]; k < rb[i + 1]; k++) {
+            const ald_trst_features &x = rows[k]; F f;
+            f.gr_vertices = x.gr_vertices; f.gr_edges = x.gr_edges; f.gr_reads = x.gr_reads; f.gr_subgraph = x.gr_subgraph; f.num_vertices = x.num_vertices; f.num_edges = x.num_edges;
+            f.junc_ratio = x.junc_ratio; f.max_mid_exon_len = x.max_mid_exon_len;
+            f.start_loss1 = x.start_loss1; f.start_loss2 = x.start_loss2; f.start_loss3 = x.start_loss3; f.end_loss1 = x.end_loss1; f.end_loss2 = x.end_loss2; f.end_loss3 = x.end_loss3;
+            f.start_merged_loss = x.start_merged_loss; f.end_merged_loss = x.end_merged_loss;
+            f.introns = x.introns; f.start_introns = x.start_introns; f.end_introns = x.end_introns; f.intron_ratio = x.intron_ratio; f.start_intron_ratio = x.start_intron_ratio; f.end_intron_ratio = x.end_intron_ratio;
+            f.uni_junc = x.uni_junc;
+            f.seq_min_wt = x.seq_min_wt; f.seq_min_cnt = x.seq_min_cnt; f.seq_min_abd = x.seq_min_abd; f.seq_min_ratio = x.seq_min_ratio;
+            f.seq_max_wt = x.seq_max_wt; f.seq_max_cnt = x.seq_max_cnt; f.seq_max_abd = x.seq_max_abd; f.seq_max_ratio = x.seq_max_ratio;
+            f.unbridge_start_coming_count = x.unbridge_start_coming_count; f.unbridge_start_coming_ratio = x.unbridge_start_coming_ratio;
+            f.unbridge_end_leaving_count = x.unbridge_end_leaving_count; f.unbridge_end_leaving_ratio = x.unbridge_end_leaving_ratio;
+            f.start_cnt = x.start_cnt; f.start_weight = x.start_weight; f.start_abd = x.start_abd; f.end_cnt = x.end_cnt; f.end_weight = x.end_weight; f.end_abd = x.end_abd;
+            out.push_back(f);
+            if(complete) complete->push_back(comp[k]);
+        }
+        return out;
+    }
 private:
+    struct graph_extras { std::vector<double> loss1, loss2, loss3, merged, leaving_ratio, coming_ratio; std::vector<int32_t> leaving_count, coming_count; int32_t reads = 0, subgraph = 0; };
+    template<class G>
+    void record_extras(int t, G &gr) {
+        if((int)extras_.size() <= t) extras_.resize((size_t)t + 1);
+        graph_extras &x = extras_[(size_t)t];
+        const int V = (int)gr.num_vertices();
+        for(int v = 0; v < V; v++) {
+            const auto &vi = gr.get_vertex_info(v);
+            x.loss1.push_back(vi.boundary_loss1); x.loss2.push_back(vi.boundary_loss2); x.loss3.push_back(vi.boundary_loss3); x.merged.push_back(vi.boundary_merged_loss);
+            x.leaving_count.push_back((int32_t)vi.unbridge_leaving_count); x.leaving_ratio.push_back(vi.unbridge_leaving_ratio);
+            x.coming_count.push_back((int32_t)vi.unbridge_coming_count); x.coming_ratio.push_back(vi.unbridge_coming_ratio);
+        }
+        x.reads = (int32_t)gr.reads; x.subgraph = (int32_t)gr.subgraph;
+    }
+    // the batch's extras, flat (graphs back to back in ticket order; zeros for a ticket enqueued without them), then the device pass
+    void compute_features() {
+        const size_t n = lpos_.size(); size_t TV = 0;
+        for(size_t t = 0; t < n; t++) TV += lpos_[t].size();
+        std::vector<double> l1(TV, 0.0), l2(TV, 0.0), l3(TV, 0.0), lm(TV, 0.0), lr(TV, 0.0), cr(TV, 0.0); std::vector<int32_t> lc(TV, 0), cc(TV, 0), rd(n, 0), sg(n, 0);
+        size_t at = 0;
+        for(size_t t = 0; t < n; t++) {
+            const size_t V = lpos_[t].size();
+            if(t < extras_.size() && extras_[t].loss1.size() == V) {
+                const graph_extras &x = extras_[t];
+                std::copy(x.loss1.begin(), x.loss1.end(), l1.begin() + at); std::copy(x.loss2.begin(), x.loss2.end(), l2.begin() + at); std::copy(x.loss3.begin(), x.loss3.end(), l3.begin() + at);
+                std::copy(x.merged.begin(), x.merged.end(), lm.begin() + at); std::copy(x.leaving_ratio.begin(), x.leaving_ratio.end(), lr.begin() + at); std::copy(x.coming_ratio.begin(), x.coming_ratio.end(), cr.begin() + at);
+                std::copy(x.leaving_count.begin(), x.leaving_count.end(), lc.begin() + at); std::copy(x.coming_count.begin(), x.coming_count.end(), cc.begin() + at);
+                rd[t] = x.reads; sg[t] = x.subgraph;
+            }
+            at += V;
+        }
+        ald_batch_extras bx;
+        bx.boundary_loss1 = l1.data(); bx.boundary_loss2 = l2.data(); bx.boundary_loss3 = l3.data(); bx.boundary_merged_loss = lm.data();
+        bx.unbridge_leaving_count = lc.data(); bx.unbridge_leaving_ratio = lr.data(); bx.unbridge_coming_count = cc.data(); bx.unbridge_coming_ratio = cr.data();
+        bx.gr_reads = rd.data(); bx.gr_subgraph = sg.data();
+        const int r = ald_batch_features_all(b_, &bx);
+        if(r != ALD_OK) throw gpu_error(r, "ald_batch_features_all");
+    }
     ald_batch *b_ = nullptr;
     std::vector<std::vector<int32_t>> lpos_, rpos_;
+    std::vector<graph_extras> extras_;              // per ticket, filled by the *_with_extras forms only
 };
 
 // the reference's single-graph shape: ctor + assemble() + .paths
@@ -222,6 +306,17 @@ public:
         batch_.flush();
         status = batch_.status(i);
         paths = batch_.paths(i);
+        return 0;
+    }
+    // opt-in: assemble() plus the feature block of every path (the reference's update_trst_features), read from gr's own objects:
+    // features[k] belongs to paths[k].  F: a type with the field names of transcript::TrstFeatures.
+    template<class F>
+    int assemble_with_features(std::vector<F> &features, int *features_status = nullptr) {
+        int i = batch_.enqueue_with_extras(gr_, hs_);
+        batch_.flush();
+        status = batch_.status(i);
+        paths = batch_.paths(i);
+        features = batch_.template features<F>(i, features_status);
         return 0;
     }
     std::vector<Path> paths;               // scallop::paths

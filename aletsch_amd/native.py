@@ -70,6 +70,49 @@ class GraphExtras(C.Structure):
         return x
 
 
+FEATURE_DTYPE = np.dtype(TrstFeatures)        # one row of ald_batch_features_table as a numpy structured dtype (same layout)
+
+
+class BatchExtras(C.Structure):
+    """ald_batch_extras: ald_graph_extras for a whole batch -- per-vertex arrays [sum of V] (graphs back to back in ticket order),
+    gr_reads / gr_subgraph [graphs]; any field may stay NULL (= zeros)"""
+    _fields_ = [("boundary_loss1", C.POINTER(_D)), ("boundary_loss2", C.POINTER(_D)), ("boundary_loss3", C.POINTER(_D)), ("boundary_merged_loss", C.POINTER(_D)),
+                ("unbridge_leaving_count", C.POINTER(_I)), ("unbridge_leaving_ratio", C.POINTER(_D)), ("unbridge_coming_count", C.POINTER(_I)),
+                ("unbridge_coming_ratio", C.POINTER(_D)), ("gr_reads", C.POINTER(_I)), ("gr_subgraph", C.POINTER(_I))]
+    VERTEX_FIELDS = ("boundary_loss1", "boundary_loss2", "boundary_loss3", "boundary_merged_loss", "unbridge_leaving_count",
+                     "unbridge_leaving_ratio", "unbridge_coming_count", "unbridge_coming_ratio")
+
+    @classmethod
+    def from_arrays(cls, **arrays):
+        """flat arrays by field name: the per-vertex ones of length sum(V), gr_reads / gr_subgraph of length #graphs"""
+        x = cls(); x._keep = []; x.arrays = {}
+        for name, a in arrays.items():
+            if a is None:
+                continue
+            t = dict(cls._fields_)[name]._type_
+            a = np.ascontiguousarray(a, np.int32 if t is _I else np.float64); x._keep.append(a); x.arrays[name] = a
+            setattr(x, name, a.ctypes.data_as(C.POINTER(t)))
+        return x
+
+    @classmethod
+    def from_graph_extras(cls, extras, g_nv):
+        """from one GraphExtras per graph (None: zeros) and the graphs' vertex counts"""
+        g_nv = np.asarray(g_nv, np.int64); off = np.concatenate([[0], np.cumsum(g_nv)]).astype(np.int64)
+        flat = {}
+        for name in cls.VERTEX_FIELDS:
+            t = dict(cls._fields_)[name]._type_
+            if not any(x is not None and bool(getattr(x, name)) for x in extras):
+                continue
+            a = np.zeros(int(off[-1]), np.int32 if t is _I else np.float64)
+            for g, x in enumerate(extras):
+                if x is not None and bool(getattr(x, name)) and g_nv[g] > 0:
+                    a[off[g]:off[g + 1]] = np.ctypeslib.as_array(getattr(x, name), shape=(int(g_nv[g]),))
+            flat[name] = a
+        flat["gr_reads"] = np.array([x.gr_reads if x is not None else 0 for x in extras], np.int32)
+        flat["gr_subgraph"] = np.array([x.gr_subgraph if x is not None else 0 for x in extras], np.int32)
+        return cls.from_arrays(**flat)
+
+
 class GraphView(C.Structure):
     """ald_graph_view (include/aletsch_decomp.h): one splice graph as caller-owned arrays"""
     _fields_ = [("num_vertices", _I), ("num_edges", _I), ("vertex_offset", C.POINTER(_I)), ("edge_target", C.POINTER(_I)), ("edge_weight", C.POINTER(_D)),
@@ -203,6 +246,9 @@ def load_library():
     lib.ald_tset_add_stream.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int64]
     lib.ald_batch_export_iterations.argtypes = [C.c_void_p, C.c_void_p]
     lib.ald_batch_features.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.ald_batch_features_all.argtypes = [C.c_void_p, C.c_void_p]
+    lib.ald_batch_features_table.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_int64)]
+    lib.ald_batch_features_stats.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     lib.ald_pre_assemble.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_void_p)]
     lib.ald_staged_view.argtypes = [C.c_void_p, C.c_void_p]
     lib.ald_staged_boundary_maps.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -417,6 +463,33 @@ class DecompBatch:
         if rc < 0:
             _check(rc)
         return [f[i] for i in range(rv.num_paths)], comp[:rv.num_paths], rc
+
+    def features_all(self, extras=None, g_nv=None):
+        """ald_batch_features_all: the feature block of every path of the batch in one call (device kernel; raw graphs by the host routine)
+        -> dict(rows = structured array of FEATURE_DTYPE [paths], complete [paths], graph_rc [graphs], row_begin [graphs + 1], stats).
+        extras: None, a BatchExtras, or a list of GraphExtras (one per graph, None = zeros) together with g_nv, the vertex counts of the
+        batch's graphs in ticket order.  The arrays are copies."""
+        if extras is not None and not isinstance(extras, BatchExtras):
+            if g_nv is None:
+                raise ValueError("features_all: a list of GraphExtras needs g_nv (the vertex count of every graph of the batch)")
+            extras = BatchExtras.from_graph_extras(extras, g_nv)
+        _check(self._lib.ald_batch_features_all(self._h, C.byref(extras) if extras is not None else None))
+        return self.features_table()
+
+    def features_table(self):
+        """the table of the last features_all (ald_batch_features_table), copied into numpy arrays"""
+        rp, cp, gp, bp, nr = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_int64()
+        _check(self._lib.ald_batch_features_table(self._h, C.byref(rp), C.byref(cp), C.byref(gp), C.byref(bp), C.byref(nr)))
+        n, m = self.n, int(nr.value)
+
+        def arr(p, k, dt):
+            if k == 0 or not p.value:
+                return np.zeros(k, dt)
+            return np.frombuffer((C.c_char * (k * np.dtype(dt).itemsize)).from_address(p.value), dt).copy()
+        st = [C.c_double(), C.c_double(), C.c_int64(), C.c_int64()]
+        _check(self._lib.ald_batch_features_stats(self._h, *[C.byref(x) for x in st]))
+        return dict(rows=arr(rp, m, FEATURE_DTYPE), complete=arr(cp, m, np.int32), graph_rc=arr(gp, n, np.int32), row_begin=arr(bp, n + 1, np.int64),
+                    stats=dict(device_ms=st[0].value, call_ms=st[1].value, device_graphs=st[2].value, host_graphs=st[3].value))
 
     def reduce_transcripts(self, sid=None, tid_base: int = 0, skip_single_exon: bool = False, single_exon_overlap: float = 0.8, into: Optional["TranscriptSink"] = None):
         """The batch's transcripts merged into an EMPTY set on the GPU (ald_batch_reduce_transcripts) -> (items in TranscriptSink.items()

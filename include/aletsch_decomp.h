@@ -260,6 +260,28 @@ typedef struct ald_graph_extras {
  * never writes them: incubator.cc:781,813), here they are zero.  Returns ALD_OK, or ALD_ST_INVARIANT + ALD_INV_OTHER (> 0) where the
  * reference would have hit one of the asserts of update_trst_features (an edge it looks up does not exist in the original graph). */
 int  ald_batch_features(const ald_batch *b, int32_t graph, const ald_graph_extras *extras, ald_trst_features *features, int32_t *complete);
+/* The same for EVERY graph of a downloaded batch in one call: one wave per graph on the device (trst_features.hip) reads the staged
+ * graphs, the path records and the result index the batch already holds in HBM; rows equal ald_batch_features bit for bit.  Raw graphs
+ * (ald_batch_add_graph_raw) take the host routine inside the same call, on up to 16 threads, since their grouped graph exists only inside
+ * the decomposition kernel.  Extras are ald_graph_extras for the whole batch: per-vertex arrays [sum of V], graphs back to back in
+ * ticket order (vertex v of graph g at the sum of the vertex counts of graphs 0..g-1, plus v); per-graph values [graphs].  Any pointer may
+ * be NULL (= zeros), and so may `x`.  ALD_ERR_STATE before ald_batch_download. */
+typedef struct ald_batch_extras {
+    const double  *boundary_loss1, *boundary_loss2, *boundary_loss3, *boundary_merged_loss;
+    const int32_t *unbridge_leaving_count; const double *unbridge_leaving_ratio;
+    const int32_t *unbridge_coming_count;  const double *unbridge_coming_ratio;
+    const int32_t *gr_reads, *gr_subgraph;
+} ald_batch_extras;
+int  ald_batch_features_all(ald_batch *b, const ald_batch_extras *x);
+/* The table of the last ald_batch_features_all, host memory owned by the batch, valid until the next upload / run / download, clear or
+ * destroy: rows[n_rows] and complete[n_rows] (as ald_batch_features fills them), graph g's rows are row_begin[g] .. row_begin[g + 1] in
+ * path order; graph_rc[graphs] = what ald_batch_features returns for the graph (ALD_OK, or ALD_ST_INVARIANT + ALD_INV_OTHER where the
+ * reference would have asserted).  Any output pointer may be NULL.  ALD_ERR_STATE when there is no table. */
+int  ald_batch_features_table(const ald_batch *b, const ald_trst_features **rows, const int32_t **complete, const int32_t **graph_rc,
+                              const int64_t **row_begin, int64_t *n_rows);
+/* of the last ald_batch_features_all: device time of the feature kernel (hipEvents), wall time of the whole call, graphs done on the
+ * device / by the host routine (raw graphs) */
+int  ald_batch_features_stats(const ald_batch *b, double *device_ms, double *call_ms, int64_t *device_graphs, int64_t *host_graphs);
 
 /* ---- GTF / feature-table writers (replace transcript::write, gtf/transcript.cc:318-360, and transcript::write_features, :362-494) ----
  * snprintf-style: write at most cap bytes (NUL-terminated when cap > 0), return the number of bytes the full text needs.

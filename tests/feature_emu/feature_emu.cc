@@ -1,0 +1,62 @@
+// feature_emu.cc -- TEST-ONLY driver of the batched feature routine (aletsch_amd/csrc/trst_features_dev.h) on one lane: the graphs are
+// staged by the product's own host_pack.h into one wire buffer (as ald_batch_upload lays it out), the given paths become records of the
+// product's layout in a pool (with a gap between them, as the pool of a real run has), and every graph goes through features_graph.
+#ifndef ALD_EMU
+#error "emulation build only"
+#endif
+#include "../../aletsch_amd/csrc/host_pack.h"
+#include "../../aletsch_amd/csrc/trst_features_dev.h"
+
+using namespace ald;
+
+extern "C" {
+
+// paths: path_offset[n+1] (paths per graph), pv_offset[paths+1] into path_vertices; extras as ald_batch_extras (any may be null);
+// lds_words: the LDS budget (0 sends every graph to the scratch).  Writes rows / complete [paths] and graph_rc [n].
+int femu_features(int32_t n, const int32_t *nv, const int32_t *ne, const int32_t *np,
+                  const int32_t *voff, const int32_t *etgt, const double *ew, const uint8_t *estrand, const double *eabd,
+                  const int32_t *esoff, const int32_t *sid, const double *sabd,
+                  const double *vw, const int32_t *lpos, const int32_t *rpos, const int32_t *vtype,
+                  const int32_t *poff, const int32_t *pv, const int32_t *pc, const char *gstrand, const int32_t *ecount, const int32_t *erank,
+                  const int64_t *path_offset, const int64_t *pv_offset, const int32_t *path_vertices, const ald_batch_extras *x, int32_t lds_words,
+                  ald_trst_features *rows, int32_t *complete, int32_t *graph_rc)
+{
+    HostBatch B;
+    int rc = B.add_packed(n, nv, ne, np, voff, etgt, ew, estrand, eabd, esoff, sid, sabd, vw, lpos, rpos, vtype, poff, pv, pc, gstrand, ecount, erank);
+    if(rc != ALD_OK) { fprintf(stderr, "femu: add_packed failed: %s\n", B.err.c_str()); return rc; }
+    HostBatch::Section sec[HostBatch::S_COUNT];
+    std::vector<uint8_t> buf(B.layout(sec));
+    B.pack_into(buf.data(), sec);
+    const int64_t total = path_offset[n];
+    // records: header + vertices, graphs in REVERSE order and 5 words of gap between records, so that nothing depends on pool order
+    std::vector<unsigned long long> index((size_t)total + 1); std::vector<long long> graph_first((size_t)n, -1); std::vector<int32_t> n_paths((size_t)n, 0);
+    std::vector<uint32_t> pool;
+    for(int g = n - 1; g >= 0; g--) {
+        n_paths[(size_t)g] = (int32_t)(path_offset[g + 1] - path_offset[g]);
+        if(n_paths[(size_t)g] > 0) graph_first[(size_t)g] = path_offset[g];
+        for(int64_t p = path_offset[g]; p < path_offset[g + 1]; p++) {
+            pool.resize(pool.size() + 5, 0xDEADBEEFu);
+            index[(size_t)p] = pool.size();
+            const int k = (int)(pv_offset[p + 1] - pv_offset[p]);
+            uint32_t hdr[REC_HDR_WORDS] = {0}; hdr[0] = (uint32_t)g; hdr[1] = (uint32_t)(p - path_offset[g]); hdr[2] = (uint32_t)k;
+            pool.insert(pool.end(), hdr, hdr + REC_HDR_WORDS);
+            for(int i = 0; i < k; i++) pool.push_back((uint32_t)path_vertices[pv_offset[p] + i]);
+        }
+    }
+    std::vector<int32_t> scratch(2 * pool.size() + 64, 0x5A5A5A5A);
+    std::vector<int32_t> lds(FT_LDS_WORDS, 0x5A5A5A5A);
+    FeatArgs A; memset(&A, 0, sizeof(A));
+    A.in = B.make_batch_in(buf.data(), sec);
+    A.pool = pool.data(); A.index = index.data(); A.graph_first = graph_first.data(); A.n_paths = n_paths.data(); A.row_begin = path_offset;
+    if(x) {
+        A.loss1 = x->boundary_loss1; A.loss2 = x->boundary_loss2; A.loss3 = x->boundary_loss3; A.merged_loss = x->boundary_merged_loss;
+        A.leaving_count = x->unbridge_leaving_count; A.leaving_ratio = x->unbridge_leaving_ratio; A.coming_count = x->unbridge_coming_count; A.coming_ratio = x->unbridge_coming_ratio;
+        A.gr_reads = x->gr_reads; A.gr_subgraph = x->gr_subgraph;
+    }
+    A.scratch = scratch.data(); A.lds_words = lds_words < FT_LDS_WORDS ? lds_words : FT_LDS_WORDS;
+    A.rows = rows; A.complete = complete; A.graph_rc = graph_rc;
+    for(int g = 0; g < n; g++) features_graph(A, g, lds.data());
+    return ALD_OK;
+}
+
+} // extern "C"
