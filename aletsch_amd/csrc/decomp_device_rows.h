@@ -207,6 +207,9 @@ enum { PF_LOAD = 0, PF_BROKEN, PF_TRIV_EVAL, PF_TRIV_MUT, PF_SMALL_EVAL, PF_SMAL
        PF_S5_DUP, PF_S5_BODY, PF_S5_RELINK, PF_S6_WALK, PF_S6_LINK, PF_S7, PF_SM_KILL, PF_SM_REEVAL, PF_COUNT };      // finer stamps inside the wave star (parts of M_mask / M_add) and the smallest-edge removal (parts of small_mut)
 
 // ---------------------------------------------------------------- small helpers
+// Every non-zero status is TERMINAL for the attempt at hand: the rule that raised it stops where it is, the graph is abandoned (or started
+// again from its input one class up) and its adjacency rows are never read again.  The row checker of the emulation (adj_check) relies on
+// that and skips a graph with a status; a status a rule could recover from would have to be kept out of HC.status, or the checker changed.
 ALD_INL void fail_(int st, int line)
 {
 #ifdef ALD_EMU
@@ -610,6 +613,7 @@ ALD_INL void kill_edge_wave(int e)
 // segment inside the pool and disjoint from the others
 static void adj_check(const char *where)
 {
+    if(HC.status) return;           // the rule stopped half way on a status word (a reference assert, a full class): the graph is abandoned, its rows are never read again
     const int nv = HC.nv; int bad = 0;
     static thread_local std::vector<int> owner; owner.assign(ADJ_CAP4, -1);
     std::vector<int> seen_in(HC.slot_hw, 0), seen_out(HC.slot_hw, 0);

@@ -21,6 +21,7 @@ struct GraphResult {
     std::vector<ora::Transcript> trsts;
     std::vector<ora::TraceEvent> trace;
     ora::Stats st;
+    ora::Census census;
     int feature_assert = 0;
 };
 
@@ -86,6 +87,7 @@ void run_one(const Packed &P, const Offsets &o, int g, const ora::Params &cfg, b
     try {
         ora::Scallop sc(gr, hs, cfg);
         if(want_trace) sc.trace = &out.trace;
+        sc.census = &out.census;
         sc.assemble();
         out.paths = sc.paths; out.trsts = sc.trsts; out.st = sc.st; out.iterations = sc.st.iterations; out.feature_assert = sc.feature_assert;
         if(sc.st.cut_short) out.status = ALD_ST_SKIPPED_LARGE;        // the loop left through `num_vertices() > max_num_exons` (scallop.cc:49), at the start or after growing
@@ -230,6 +232,18 @@ int ora_result_stats(const ora_result *R, int32_t *stats6)
         int32_t *o = stats6 + 6 * g;
         o[0] = s.max_live_edges; o[1] = s.max_vertices; o[2] = s.total_edge_ids; o[3] = s.iterations; o[4] = s.router_builds; o[5] = s.max_mev;
     }
+    return 0;
+}
+
+/* census of one graph's run (scallop_oracle.hpp: Census): *n_rows rows of 7 ints = the six key fields + the number of events; rows7 == null asks
+ * for the number of rows only.  A graph that ended on an assert class reports what it met up to there. */
+int ora_result_census(const ora_result *R, int32_t graph, int32_t *n_rows, int32_t *rows7, int32_t cap)
+{
+    const ora::Census &c = R->gr[graph].census;
+    *n_rows = (int32_t)c.size();
+    if(!rows7) return 0;
+    int i = 0;
+    for(auto &kv : c) { if(i >= cap) break; for(int k = 0; k < 6; k++) rows7[7 * i + k] = kv.first[k]; rows7[7 * i + 6] = kv.second; i++; }
     return 0;
 }
 

@@ -33,6 +33,7 @@
 #include <vector>
 #include <set>
 #include <map>
+#include <array>
 #include <tuple>
 #include <algorithm>
 #include <cmath>
@@ -761,6 +762,11 @@ enum { OP_BROKEN = 1, OP_TRIVIAL_FAST = 2, OP_TRIVIAL_NOW = 3, OP_TRIVIAL_BEST =
        OP_UNSPLIT_NOW = 7, OP_UNSPLIT_BEST = 8, OP_GREEDY = 9, OP_COLLECT = 10 };
 
 struct Stats { int max_live_edges = 0, max_vertices = 0, total_edge_ids = 0, iterations = 0, router_builds = 0, max_mev = 0, cut_short = 0; };
+// Which shapes the run met, for the tests that must know which form of the kernel a batch exercises (the kernel chooses its code path by
+// the degrees of the vertex at hand; equal records mean equal sequences of graph states, so this census is the kernel's as well).
+//   trivial decompositions: {0, direction (0: one in-edge, the fan goes out; 1: one out-edge, the fan comes in), fan size, 0, 0, 0}
+//   router builds:          {1, in-degree, out-degree, graph has phasing lists, every counted edge has ONE sample, some edge has count 0}
+typedef std::map<std::array<int, 6>, int> Census;
 
 // ---------------------------------------------------------------------------------------------
 // scallop (scallop/scallop.cc)
@@ -770,7 +776,7 @@ struct Scallop {
     std::vector<std::vector<int>> mev; std::vector<double> med; std::vector<int> mei;
     std::vector<int> v2v; std::set<int> nonzeroset;
     std::vector<Path> paths; std::vector<Transcript> trsts;
-    std::vector<TraceEvent> *trace = nullptr; Stats st;
+    std::vector<TraceEvent> *trace = nullptr; Stats st; Census *census = nullptr;        // where the caller wants the census (it outlives a run that ends on an assert)
     Graph gr_ori;
     int feature_assert = 0;                     // line of the first assert update_trst_features would have hit (0: none); the paths stand either way
 
@@ -942,7 +948,7 @@ struct Scallop {
             rt.classify();
             if(rt.type != type) continue;
             if(rt.degree > degree) continue;
-            rt.build(); st.router_builds++;
+            census_router(i); rt.build(); st.router_builds++;
             if(rt.ratio < 0.01) {
                 ev(OP_UNSPLIT_NOW, i, type, rt.ratio);
                 decompose_vertex_extend(i, rt.pe2w);
@@ -1069,7 +1075,16 @@ struct Scallop {
         ORA_ASSERT(INV_DEGREE, gr.degree(root) == 0);
         nonzeroset.erase(root);
     }
+    void census_router(int x) {
+        if(!census) return;
+        bool single = true, zero = false;
+        for(int side = 0; side < 2; side++) for(int e : (side == 0 ? gr.in_edges(x) : gr.out_edges(x))) {
+            if(gr.einf[e].count == 0) zero = true; else if(gr.einf[e].samples.size() != 1) single = false;
+        }
+        (*census)[{1, gr.in_degree(x), gr.out_degree(x), hs.edges.empty() ? 0 : 1, single ? 1 : 0, zero ? 1 : 0}]++;
+    }
     void decompose_trivial_vertex(int x) {      // scallop.cc:2144-2167
+        if(census) { if(gr.in_degree(x) == 1) (*census)[{0, 0, gr.out_degree(x), 0, 0, 0}]++; else (*census)[{0, 1, gr.in_degree(x), 0, 0, 0}]++; }
         balance_vertex(x);
         MPID pe2w;
         for(int e1 : gr.in_edges(x)) { double w1 = gr.ewrt[e1];
