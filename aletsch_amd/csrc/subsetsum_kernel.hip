@@ -4,10 +4,14 @@
 // last-item back-pointers per side (table[i][j]), merges the achievable sums of both sides, picks the closest
 // cross pair and back-traces it.  Here the DP rows are filled 64 sums per step (lane = sum j), the achievable
 // sums of both sides are compacted into one ordered list with ballot + popcount prefix sums, and the closest
-// cross pair is a wave arg-min.  Tables are u8 back-pointers in LDS (2 sides x 33 rows x 1000 sums = 66 KB).
+// cross pair is a wave arg-min.  Tables are u8 back-pointers in LDS: 2 sides x 33 rows x SS_MAXS = 1040 sums = 68 640 bytes, and with the
+// list of achievable sums (2 x 1040 sums of 4 bytes + 1 byte of tag) and the items a block holds 79 576 bytes (about 80 KB), so two blocks fit the 160 KB of a CU.
 //
 // This component is dead in the reference's live path and is wired here exactly as a separately
 // KAT-checked kernel (tests/test_gpu_parity.py::test_subsetsum_kernel_matches_reference_golden, tests/test_oracle_pins.py: reference KAT subsetsum.cc:263-282 + oracle/_ref/ref_subsetsum).
+// Pinned over its whole domain -- 1..32 items a side, bumped items up to ub = 1029, dense lists, ties, sort order, refused and out-of-range
+// instances, blocks that run several instances in turn -- by tests/test_subsetsum_gpu.py (kernel against the reference's stored answers and
+// the oracle) and tests/test_subsetsum_cpu.py (oracle against the same answers); instance families: tests/subsetsum_cases.py.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <string>
