@@ -37,11 +37,12 @@ struct StagedPass {
 // the feature table of the last ald_batch_features_all (trst_features.hip): host rows in pinned memory, valid until the next download / clear
 struct FeatTable {
     DevBuf d_rows, d_complete, d_rc, d_scratch, d_x[10];
+    DevBuf d_gew, d_gecount, d_gdead, d_glive;     // ALD_FEAT_RAW_ON_DEVICE: the grouped-graph overlay of the raw graphs (weight / count / dead flag per edge of the batch, live edges per graph)
     PinBuf h_rows, h_complete, h_rc;
     std::vector<int64_t> row_begin;
     hipEvent_t e0 = nullptr, e1 = nullptr;
     bool valid = false; double device_ms = 0, call_ms = 0; int64_t device_graphs = 0, host_graphs = 0, n_rows = 0;
-    void release() { DevBuf *d[] = {&d_rows, &d_complete, &d_rc, &d_scratch}; for(DevBuf *x : d) x->release(); for(DevBuf &x : d_x) x.release();
+    void release() { DevBuf *d[] = {&d_rows, &d_complete, &d_rc, &d_scratch, &d_gew, &d_gecount, &d_gdead, &d_glive}; for(DevBuf *x : d) x->release(); for(DevBuf &x : d_x) x.release();
                      h_rows.release(); h_complete.release(); h_rc.release(); if(e0) hipEventDestroy(e0); if(e1) hipEventDestroy(e1); e0 = e1 = nullptr; valid = false; }
 };
 

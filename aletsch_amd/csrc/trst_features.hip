@@ -6,7 +6,8 @@
 // sections of d_in), the path records (d_pool) and the result index (d_index / d_gfirst) the batch already holds, plus the caller's
 // extras.  The rows equal the host routine ald_batch_features (trst_features.cpp) bit for bit.  Raw graphs -- whose grouped graph exists
 // only inside the decomposition kernel's raw build -- take that host routine inside the same call, on up to 16 host threads, while the
-// kernel runs; their rows land in the same table.
+// kernel runs; their rows land in the same table.  With ALD_FEAT_RAW_ON_DEVICE (ald_batch_features_all_ex) their wave instead rebuilds
+// the grouped graph as an overlay of the wire edges (trst_features_dev.h: ft_group_boundaries) and no host thread computes a row.
 #include "tset_front.h"
 #include "trst_features_dev.h"
 #include <chrono>
@@ -28,9 +29,13 @@ __global__ void __launch_bounds__(64) trst_feature_waves(ald::FeatArgs A)
 
 extern "C" {
 
-int ald_batch_features_all(ald_batch *b, const ald_batch_extras *x)
+int ald_batch_features_all(ald_batch *b, const ald_batch_extras *x) { return ald_batch_features_all_ex(b, x, 0); }
+
+int ald_batch_features_all_ex(ald_batch *b, const ald_batch_extras *x, uint32_t flags)
 {
     if(!b) return ALD_ERR_INVALID;
+    if(flags & ~ALD_FEAT_RAW_ON_DEVICE) return ald_set_err(ALD_ERR_INVALID, "ald_batch_features_all_ex: unknown flag bits");
+    const bool raw_dev = (flags & ALD_FEAT_RAW_ON_DEVICE) != 0;
     if(!b->downloaded) return ald_set_err(ALD_ERR_STATE, "ald_batch_features_all before ald_batch_download");
     const auto T0 = std::chrono::steady_clock::now();
     FeatTable &T = b->feat;
@@ -47,10 +52,11 @@ int ald_batch_features_all(ald_batch *b, const ald_batch_extras *x)
         return ald_set_err(ALD_ERR_NOMEM, "pinned feature table");
     int32_t *h_rc = (int32_t*)T.h_rc.p;
     std::vector<int32_t> raw;
-    for(int g = 0; g < n; g++) if(hb.g_rawdist[(size_t)g] >= 0) raw.push_back(g);
+    bool raw_paths = false;                                                      // ALD_FEAT_RAW_ON_DEVICE: some raw graph has a path, i.e. needs its overlay
+    for(int g = 0; g < n; g++) if(hb.g_rawdist[(size_t)g] >= 0) { if(!raw_dev) raw.push_back(g); else if(T.row_begin[(size_t)g + 1] > T.row_begin[(size_t)g]) raw_paths = true; }
     T.host_graphs = (int64_t)raw.size(); T.device_graphs = (int64_t)n - T.host_graphs;
 
-    // ---- the device part: every staged graph with at least one path, one wave each
+    // ---- the device part: every staged graph (ALD_FEAT_RAW_ON_DEVICE: every graph) with at least one path, one wave each
     const bool launch = rows > 0 && T.device_graphs > 0;
     if(launch) {
         { int rc = device_path_table(b); if(rc != ALD_OK) return rc; }          // d_pbegin: first row of every graph, from the kernel's counts
@@ -90,6 +96,11 @@ int ald_batch_features_all(ald_batch *b, const ald_batch_extras *x)
             const uint64_t words = b->res.ext_words ? b->res.ext_words : b->pool_cap_words;
             if(T.d_scratch.ensure(8 * (size_t)words + 256)) return ald_set_err(ALD_ERR_NOMEM, "feature scratch");
             A.scratch = (int32_t*)T.d_scratch.p;
+        }
+        if(raw_paths) {                                                          // the overlay: per edge of the batch at off_e[g] + k, per graph
+            const size_t TE = (size_t)hb.off_e[(size_t)n];
+            if(T.d_gew.ensure(8 * TE + 64) || T.d_gecount.ensure(4 * TE + 64) || T.d_gdead.ensure(TE + 64) || T.d_glive.ensure(4 * (size_t)n + 64)) return ald_set_err(ALD_ERR_NOMEM, "feature overlay of the raw graphs");
+            A.g_ew = (ALD_GLOBAL double*)T.d_gew.p; A.g_ecount = (ALD_GLOBAL int32_t*)T.d_gecount.p; A.g_dead = (ALD_GLOBAL uint8_t*)T.d_gdead.p; A.g_live = (ALD_GLOBAL int32_t*)T.d_glive.p;
         }
         if(T.d_rows.ensure(RB * (size_t)rows + 64) || T.d_complete.ensure(4 * (size_t)rows + 64) || T.d_rc.ensure(4 * (size_t)n + 64)) return ald_set_err(ALD_ERR_NOMEM, "feature table");
         A.rows = (ALD_GLOBAL ald_trst_features*)T.d_rows.p; A.complete = (ALD_GLOBAL int32_t*)T.d_complete.p; A.graph_rc = (ALD_GLOBAL int32_t*)T.d_rc.p;
@@ -140,6 +151,7 @@ int ald_batch_features_all(ald_batch *b, const ald_batch_extras *x)
     if(launch) {
         HCHK(hipStreamSynchronize(b->stream));
         float ms = 0; if(hipEventElapsedTime(&ms, T.e0, T.e1) == hipSuccess) T.device_ms = ms;
+        if(raw_dev && !raw_paths) for(int g = 0; g < n; g++) if(hb.g_rawdist[(size_t)g] >= 0) h_rc[g] = ALD_OK;      // no overlay, no wave work: raw graphs without paths
     } else for(int g = 0; g < n; g++) h_rc[g] = ALD_OK;                    // no paths on the device side: nothing can assert
     if(hard_err.load() < 0) return ald_set_err(hard_err.load(), "ald_batch_features on a raw graph failed");
     ald_trst_features *h_rows = (ald_trst_features*)T.h_rows.p; int32_t *h_complete = (int32_t*)T.h_complete.p;

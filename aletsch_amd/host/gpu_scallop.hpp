@@ -218,9 +218,13 @@ public:
     int enqueue_raw_with_extras(G &gx, const PhaseSet &px, int max_group_boundary_distance = 10000) { const int t = enqueue_raw(gx, px, max_group_boundary_distance); record_extras(t, gx); return t; }
     // After flush(): the features of every path of ticket i, in path order, in a caller type F with the field names of the reference's
     // transcript::TrstFeatures (gtf/transcript.h:60-104) -- what build_transcripts puts into trst.features before ts.add.  The whole batch
-    // is computed by the first call after a flush (ald_batch_features_all: one device pass; raw graphs by the host routine).  `status`
+    // is computed by the first call after a flush (ald_batch_features_all_ex: one device pass; raw graphs by the host routine, or, after
+    // features_raw_on_device(true), by the same device pass).  `status`
     // receives what the reference's asserts would have said (ALD_OK, or ALD_ST_INVARIANT + ALD_INV_OTHER); `complete` (optional): 0 for
     // a path without a junction, whose fields past the first seven the reference never sets.
+    // raw tickets (enqueue_raw) in the device pass as well (ALD_FEAT_RAW_ON_DEVICE): the kernel folds their boundaries itself instead of the
+    // host re-running the pre-steps per graph.  Same values; takes effect at the next computation of the table.  Default: false.
+    void features_raw_on_device(bool on) { feat_raw_on_device_ = on; }
     template<class F>
     std::vector<F> features(int i, int *status = nullptr, std::vector<int> *complete = nullptr) {
         const ald_trst_features *rows = nullptr; const int32_t *comp = nullptr, *rc = nullptr; const int64_t *rb = nullptr; int64_t nr = 0;
@@ -287,10 +291,11 @@ private:
         bx.boundary_loss1 = l1.data(); bx.boundary_loss2 = l2.data(); bx.boundary_loss3 = l3.data(); bx.boundary_merged_loss = lm.data();
         bx.unbridge_leaving_count = lc.data(); bx.unbridge_leaving_ratio = lr.data(); bx.unbridge_coming_count = cc.data(); bx.unbridge_coming_ratio = cr.data();
         bx.gr_reads = rd.data(); bx.gr_subgraph = sg.data();
-        const int r = ald_batch_features_all(b_, &bx);
-        if(r != ALD_OK) throw gpu_error(r, "ald_batch_features_all");
+        const int r = ald_batch_features_all_ex(b_, &bx, feat_raw_on_device_ ? ALD_FEAT_RAW_ON_DEVICE : 0u);
+        if(r != ALD_OK) throw gpu_error(r, "ald_batch_features_all_ex");
     }
     ald_batch *b_ = nullptr;
+    bool feat_raw_on_device_ = false;
     std::vector<std::vector<int32_t>> lpos_, rpos_;
     std::vector<graph_extras> extras_;              // per ticket, filled by the *_with_extras forms only
 };

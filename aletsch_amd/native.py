@@ -70,6 +70,7 @@ class GraphExtras(C.Structure):
         return x
 
 
+FEAT_RAW_ON_DEVICE = 1                        # ALD_FEAT_RAW_ON_DEVICE (ald_batch_features_all_ex)
 FEATURE_DTYPE = np.dtype(TrstFeatures)        # one row of ald_batch_features_table as a numpy structured dtype (same layout)
 
 
@@ -247,6 +248,7 @@ def load_library():
     lib.ald_batch_export_iterations.argtypes = [C.c_void_p, C.c_void_p]
     lib.ald_batch_features.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.ald_batch_features_all.argtypes = [C.c_void_p, C.c_void_p]
+    lib.ald_batch_features_all_ex.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
     lib.ald_batch_features_table.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_int64)]
     lib.ald_batch_features_stats.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     lib.ald_pre_assemble.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_void_p)]
@@ -464,8 +466,9 @@ class DecompBatch:
             _check(rc)
         return [f[i] for i in range(rv.num_paths)], comp[:rv.num_paths], rc
 
-    def features_all(self, extras=None, g_nv=None):
-        """ald_batch_features_all: the feature block of every path of the batch in one call (device kernel; raw graphs by the host routine)
+    def features_all(self, extras=None, g_nv=None, raw_on_device: bool = False):
+        """ald_batch_features_all_ex: the feature block of every path of the batch in one call (device kernel; raw graphs by the host
+        routine, or -- raw_on_device, ALD_FEAT_RAW_ON_DEVICE -- by the kernel as well, which then folds their boundaries itself)
         -> dict(rows = structured array of FEATURE_DTYPE [paths], complete [paths], graph_rc [graphs], row_begin [graphs + 1], stats).
         extras: None, a BatchExtras, or a list of GraphExtras (one per graph, None = zeros) together with g_nv, the vertex counts of the
         batch's graphs in ticket order.  The arrays are copies."""
@@ -473,7 +476,7 @@ class DecompBatch:
             if g_nv is None:
                 raise ValueError("features_all: a list of GraphExtras needs g_nv (the vertex count of every graph of the batch)")
             extras = BatchExtras.from_graph_extras(extras, g_nv)
-        _check(self._lib.ald_batch_features_all(self._h, C.byref(extras) if extras is not None else None))
+        _check(self._lib.ald_batch_features_all_ex(self._h, C.byref(extras) if extras is not None else None, C.c_uint32(FEAT_RAW_ON_DEVICE if raw_on_device else 0)))
         return self.features_table()
 
     def features_table(self):

@@ -273,6 +273,15 @@ typedef struct ald_batch_extras {
     const int32_t *gr_reads, *gr_subgraph;
 } ald_batch_extras;
 int  ald_batch_features_all(ald_batch *b, const ald_batch_extras *x);
+/* The same with options; ald_batch_features_all(b, x) is ald_batch_features_all_ex(b, x, 0).  ALD_FEAT_RAW_ON_DEVICE: raw graphs are done by
+ * the kernel as well.  Of the pre-steps only group_start_boundaries / group_end_boundaries (rnacore/graph_reviser.cc:916-1066) change what
+ * the features read, so the wave of a raw graph first folds the boundaries into an overlay of the wire edges (weight, count, a dead flag
+ * per edge, the live edge count) and then reads the grouped graph through it; no host thread computes a row, ald_pre_assemble is not
+ * called, and ald_batch_features_stats reports host_graphs = 0.  Rows equal ald_batch_features bit for bit; graph_rc too, except for a raw
+ * graph on which the pre-steps asserted: it has no paths and reports ALD_OK here, where ald_batch_features repeats the assert's status.
+ * Any other flag bit: ALD_ERR_INVALID. */
+#define ALD_FEAT_RAW_ON_DEVICE 1u
+int  ald_batch_features_all_ex(ald_batch *b, const ald_batch_extras *x, uint32_t flags);
 /* The table of the last ald_batch_features_all, host memory owned by the batch, valid until the next upload / run / download, clear or
  * destroy: rows[n_rows] and complete[n_rows] (as ald_batch_features fills them), graph g's rows are row_begin[g] .. row_begin[g + 1] in
  * path order; graph_rc[graphs] = what ald_batch_features returns for the graph (ALD_OK, or ALD_ST_INVARIANT + ALD_INV_OTHER where the
