@@ -335,7 +335,7 @@ int ald_batch_destroy(ald_batch *b)
 int ald_batch_clear(ald_batch *b)
 {
     if(!b) return ALD_ERR_INVALID;
-    b->hb.clear(); b->res.clear(); b->uploaded = b->ran = b->downloaded = false; b->kernel_ms = -1; b->feat.valid = false;
+    b->hb.clear(); b->res.clear(); b->uploaded = b->ran = b->downloaded = b->finished = false; b->kernel_ms = -1; b->feat.valid = false;
     return ALD_OK;
 }
 
@@ -349,7 +349,7 @@ static int staging_out_of_memory(ald_batch *b)
 int ald_batch_add_graph(ald_batch *b, const ald_graph_view *g)
 {
     if(!b || !g) return ALD_ERR_INVALID;
-    b->uploaded = b->ran = b->downloaded = false;
+    b->uploaded = b->ran = b->downloaded = b->finished = false;
     int rc;
     try { rc = b->hb.add_graph(*g); } catch(const std::bad_alloc &) { return staging_out_of_memory(b); }
     if(rc != ALD_OK) return set_err(rc, b->hb.err);
@@ -364,7 +364,7 @@ int ald_batch_add_packed(ald_batch *b, int32_t n, const int32_t *g_nv, const int
                          const int32_t *edge_creation_rank)
 {
     if(!b || n < 0 || !g_nv || !g_ne) return ALD_ERR_INVALID;
-    b->uploaded = b->ran = b->downloaded = false;
+    b->uploaded = b->ran = b->downloaded = b->finished = false;
     int rc;
     try { rc = b->hb.add_packed(n, g_nv, g_ne, g_np, vertex_offset, edge_target, edge_weight, edge_strand, edge_abd, edge_sample_offset, sample_id, sample_abd,
                               vertex_weight, vertex_lpos, vertex_rpos, vertex_type, phasing_offset, phasing_vertex, phasing_count, graph_strand, edge_count, edge_creation_rank); }
@@ -382,7 +382,7 @@ int ald_batch_add_packed_raw(ald_batch *b, int32_t n, const int32_t *g_nv, const
                              const int32_t *raw_max_group_boundary_distance, const int32_t *g_nphase, const int32_t *phase_offset, const int32_t *phase_coord, const int32_t *phase_count)
 {
     if(!b || n < 0 || !g_nv || !g_ne) return ALD_ERR_INVALID;
-    b->uploaded = b->ran = b->downloaded = false;
+    b->uploaded = b->ran = b->downloaded = b->finished = false;
     int rc;
     try { rc = b->hb.add_packed_raw(n, g_nv, g_ne, g_np, vertex_offset, edge_target, edge_weight, edge_strand, edge_abd, edge_sample_offset, sample_id, sample_abd,
                                   vertex_weight, vertex_lpos, vertex_rpos, vertex_type, phasing_offset, phasing_vertex, phasing_count, graph_strand, edge_count, edge_creation_rank,
@@ -502,7 +502,7 @@ int ald_batch_upload(ald_batch *b)
         b->pass0_on_device = true;
     }
     HIPCHK(hipStreamSynchronize(us));             // (a batch without work never reached push_pass)
-    b->uploaded = true; b->ran = false; b->downloaded = false;
+    b->uploaded = true; b->ran = false; b->downloaded = b->finished = false;
     return ALD_OK;
 }
 
@@ -528,7 +528,7 @@ static int start_run(ald_batch *b)
     if(!b->pass0_on_device) { int rc = push_pass(b, *b->pass0); if(rc != ALD_OK) return rc; b->pass0_on_device = true; }      // a retry pass of the last run used the buffers
     int rc = fire_pass(b, *b->pass0);
     if(rc != ALD_OK) return rc;
-    b->ran = true; b->downloaded = false;
+    b->ran = true; b->downloaded = b->finished = false;
     return ALD_OK;
 }
 
@@ -540,32 +540,33 @@ int ald_batch_sync(ald_batch *b)
     return ALD_OK;
 }
 
-int ald_batch_download(ald_batch *b)
+namespace {
+typedef std::chrono::steady_clock::time_point ald_tp;
+double ms_between(ald_tp a, ald_tp c) { return std::chrono::duration<double, std::milli>(c - a).count(); }
+struct EndStamps { ald_tp P1, P2; int64_t bytes = 0; };      // the kernels of pass 0 are through / its status words are here; bytes moved to the host
+
+// The stage that ENDS a run, shared by ald_batch_finish and ald_batch_download: wait for the stream, status words, capacity retries one
+// class up, pool growth and a new run on ALD_ST_POOL_FULL, then the two counters.  Leaves b->status, b->used_words / used_index (clamped).
+// Everything comes back through async copies on the batch's OWN stream into pinned memory.  (A synchronous hipMemcpy runs on the
+// null stream, which waits for every blocking stream of the device -- i.e. for the kernel of the NEXT batch, already in flight in a
+// pipelined caller: the download of batch k took as long as the kernel of batch k+1, and its record copy ran between two kernels.)
+int end_run(ald_batch *b, EndStamps &T)
 {
-    if(!b) return ALD_ERR_INVALID;
-    if(!b->ran) return set_err(ALD_ERR_STATE, "ald_batch_download before ald_batch_run");
-    HIPCHK(hipSetDevice(b->device));
     const int n = b->hb.n();
-    b->feat.valid = false;
-    const bool prof = getenv("ALD_DOWNLOAD_PROF") != nullptr; const auto P0 = std::chrono::steady_clock::now(); auto P1 = P0, P2 = P0, P3 = P0;
-    b->n_paths.assign(n, 0); b->n_iters.assign(n, 0);
-    // Everything comes back through async copies on the batch's OWN stream into pinned memory.  (A synchronous hipMemcpy runs on the
-    // null stream, which waits for every blocking stream of the device -- i.e. for the kernel of the NEXT batch, already in flight in a
-    // pipelined caller: the download of batch k took as long as the kernel of batch k+1, and its record copy ran between two kernels.)
+    T.P1 = T.P2 = std::chrono::steady_clock::now(); T.bytes = 0;
     if(b->pin_small.ensure(64 + 20 * (size_t)n + 64, true)) return set_err(ALD_ERR_NOMEM, "pinned status buffer");
     unsigned long long *h_used = (unsigned long long*)b->pin_small.p;
-    long long *h_gf = (long long*)((uint8_t*)b->pin_small.p + 64);
-    int32_t *st = (int32_t*)(h_gf + n), *h_np = st + n, *h_ni = h_np + n;
+    int32_t *st = (int32_t*)((long long*)((uint8_t*)b->pin_small.p + 64) + n);
     unsigned long long used = 0, iused = 0;
   for(int regrow = 0; ; regrow++) {
     bool pool_full = false;
     for(int pass = 0; pass <= ALD_NUM_CLASSES; pass++) {
         HIPCHK(hipStreamSynchronize(b->stream));
-        if(pass == 0 && regrow == 0) P1 = std::chrono::steady_clock::now();
+        if(pass == 0 && regrow == 0) T.P1 = std::chrono::steady_clock::now();
         float ms = 0; if(hipEventElapsedTime(&ms, b->ev0, b->ev1) == hipSuccess) b->kernel_ms += ms;
         b->passes++;
-        if(n > 0) { HIPCHK(hipMemcpyAsync(st, b->d_status.p, 4 * (size_t)n, hipMemcpyDeviceToHost, b->stream)); HIPCHK(hipStreamSynchronize(b->stream)); }
-        if(pass == 0 && regrow == 0) P2 = std::chrono::steady_clock::now();
+        if(n > 0) { HIPCHK(hipMemcpyAsync(st, b->d_status.p, 4 * (size_t)n, hipMemcpyDeviceToHost, b->stream)); HIPCHK(hipStreamSynchronize(b->stream)); T.bytes += 4 * (int64_t)n; }
+        if(pass == 0 && regrow == 0) T.P2 = std::chrono::steady_clock::now();
         // graphs whose working set overflowed their class are retried one class up (records carry the pass number)
         std::vector<int32_t> work[ALD_NUM_CLASSES]; bool any = false;
         for(int g = 0; g < n; g++) {
@@ -580,7 +581,7 @@ int ald_batch_download(ald_batch *b)
         int rc = launch_pass(b, work, pass + 1);
         if(rc != ALD_OK) return rc;
     }
-    HIPCHK(hipMemcpyAsync(h_used, b->d_poolused.p, 16, hipMemcpyDeviceToHost, b->stream)); HIPCHK(hipStreamSynchronize(b->stream)); used = h_used[0]; iused = h_used[1];
+    HIPCHK(hipMemcpyAsync(h_used, b->d_poolused.p, 16, hipMemcpyDeviceToHost, b->stream)); HIPCHK(hipStreamSynchronize(b->stream)); used = h_used[0]; iused = h_used[1]; T.bytes += 16;
     if(!pool_full) break;
     // Some graph found the record pool full.  Records behind the first refused one may be missing (the bump pointer moved, nothing was
     // written), so the stream of this run is unusable as a whole: the pool grows -- `used` counts every request made, a lower bound
@@ -597,21 +598,108 @@ int ald_batch_download(ald_batch *b)
   }
     if(used > b->pool_cap_words) used = b->pool_cap_words;
     if(iused > b->index_cap) iused = b->index_cap;
+    b->used_words = used; b->used_index = iused;
+    return ALD_OK;
+}
+
+// the per-graph counters: 16 bytes per graph, enqueued behind whatever the caller put on the batch's stream (which it then waits for)
+int enqueue_counters(ald_batch *b)
+{
+    const int n = b->hb.n();
+    if(n == 0) return ALD_OK;
+    long long *h_gf = (long long*)((uint8_t*)b->pin_small.p + 64);
+    int32_t *h_np = (int32_t*)(h_gf + n) + n, *h_ni = h_np + n;
+    HIPCHK(hipMemcpyAsync(h_np, b->d_npaths.p, 4 * (size_t)n, hipMemcpyDeviceToHost, b->stream));
+    HIPCHK(hipMemcpyAsync(h_ni, b->d_niters.p, 4 * (size_t)n, hipMemcpyDeviceToHost, b->stream));
+    HIPCHK(hipMemcpyAsync(h_gf, b->d_gfirst.p, 8 * (size_t)n, hipMemcpyDeviceToHost, b->stream));
+    return ALD_OK;
+}
+void take_counters(ald_batch *b)
+{
+    const int n = b->hb.n();
+    const int32_t *h_np = (const int32_t*)((const long long*)((const uint8_t*)b->pin_small.p + 64) + n) + n, *h_ni = h_np + n;
+    b->n_paths.assign(n, 0); b->n_iters.assign(n, 0);
+    if(n > 0) { memcpy(b->n_paths.data(), h_np, 4 * (size_t)n); memcpy(b->n_iters.data(), h_ni, 4 * (size_t)n); }
+}
+} // namespace
+
+int ald_batch_finish(ald_batch *b)
+{
+    if(!b) return ALD_ERR_INVALID;
+    if(!b->ran) return set_err(ALD_ERR_STATE, "ald_batch_finish before ald_batch_run");
+    if(b->finished || b->downloaded) return ALD_OK;        // the run has ended already
+    HIPCHK(hipSetDevice(b->device));
+    const int n = b->hb.n();
+    b->feat.valid = false;
+    const auto P0 = std::chrono::steady_clock::now();
+    EndStamps T;
+    { int rc = end_run(b, T); if(rc != ALD_OK) return rc; }
+    { int rc = enqueue_counters(b); if(rc != ALD_OK) return rc; }
+    HIPCHK(hipStreamSynchronize(b->stream));
+    take_counters(b);
+    // the row prefix of the (graph, path) order, exactly as HostResults::build forms it: only graphs that ended well have paths
+    const long long *h_gf = (const long long*)((const uint8_t*)b->pin_small.p + 64);
+    b->path_begin.assign((size_t)n + 1, 0);
+    for(int g = 0; g < n; g++) {
+        const bool ok = b->status[g] == ALD_ST_OK || b->status[g] == ALD_ST_SKIPPED_LARGE;
+        const int64_t c = ok ? b->n_paths[g] : 0;
+        if(c < 0 || (c > 0 && (h_gf[g] < 0 || (uint64_t)h_gf[g] + (uint64_t)c > b->used_index))) return set_err(ALD_ERR_STATE, "result index is inconsistent with the path counts of graph " + std::to_string(g));
+        b->path_begin[(size_t)g + 1] = b->path_begin[(size_t)g] + c;
+    }
+    b->total_paths = b->path_begin[(size_t)n]; b->paths_on_device = false;
+    b->fin_ms[0] = ms_between(P0, T.P1); b->fin_ms[1] = ms_between(T.P1, std::chrono::steady_clock::now()); b->fin_bytes = T.bytes + 16 * (int64_t)n;
+    b->finished = true;
+    return ALD_OK;
+}
+
+int ald_batch_last_finish_ms(const ald_batch *b, double *wait_kernel_ms, double *status_retries_ms, int64_t *bytes_to_host)
+{
+    if(!b) return ALD_ERR_INVALID;
+    if(wait_kernel_ms) *wait_kernel_ms = b->fin_ms[0]; if(status_retries_ms) *status_retries_ms = b->fin_ms[1];
+    if(bytes_to_host) *bytes_to_host = b->fin_bytes;
+    return ALD_OK;
+}
+
+int ald_batch_export_status(const ald_batch *b, int32_t *status, int32_t *num_paths, int32_t *num_iterations)
+{
+    if(!b) return ALD_ERR_INVALID;
+    if(!b->finished && !b->downloaded) return set_err(ALD_ERR_STATE, "ald_batch_export_status before ald_batch_finish / ald_batch_download");
+    const std::vector<int64_t> &pb = b->downloaded ? b->res.path_begin : b->path_begin;
+    for(int g = 0; g < b->hb.n(); g++) {
+        if(status) status[g] = b->status[g];
+        if(num_paths) num_paths[g] = (int32_t)(pb[(size_t)g + 1] - pb[(size_t)g]);
+        if(num_iterations) num_iterations[g] = b->n_iters[g];
+    }
+    return ALD_OK;
+}
+
+int ald_batch_download(ald_batch *b)
+{
+    if(!b) return ALD_ERR_INVALID;
+    if(!b->ran) return set_err(ALD_ERR_STATE, "ald_batch_download before ald_batch_run");
+    HIPCHK(hipSetDevice(b->device));
+    const int n = b->hb.n();
+    b->feat.valid = false;
+    const bool prof = getenv("ALD_DOWNLOAD_PROF") != nullptr; const auto P0 = std::chrono::steady_clock::now(); auto P1 = P0, P2 = P0, P3 = P0;
+    const bool ended = b->finished;                        // ald_batch_finish went before: status, retries and counters are in
+    if(!ended) {
+        EndStamps T;
+        { int rc = end_run(b, T); if(rc != ALD_OK) return rc; }
+        P1 = T.P1; P2 = T.P2;
+    }
+    const unsigned long long used = b->used_words, iused = b->used_index;
+    long long *h_gf = (long long*)((uint8_t*)b->pin_small.p + 64);
     b->res.clear();
     // the records land in a pinned buffer (kept across runs) through an async copy on the batch stream: the copy engine moves them
     // while another batch's kernel may be running, and the host thread only waits
     if(b->pin_out.ensure(4 * (size_t)used + 64, true) || b->pin_index.ensure(8 * (size_t)iused + 64, true)) return set_err(ALD_ERR_NOMEM, "pinned result buffer");
     P3 = std::chrono::steady_clock::now();
-    if(n > 0) {
-        HIPCHK(hipMemcpyAsync(h_np, b->d_npaths.p, 4 * (size_t)n, hipMemcpyDeviceToHost, b->stream));
-        HIPCHK(hipMemcpyAsync(h_ni, b->d_niters.p, 4 * (size_t)n, hipMemcpyDeviceToHost, b->stream));
-        HIPCHK(hipMemcpyAsync(h_gf, b->d_gfirst.p, 8 * (size_t)n, hipMemcpyDeviceToHost, b->stream));
-    }
+    if(!ended) { int rc = enqueue_counters(b); if(rc != ALD_OK) return rc; }
     if(iused) HIPCHK(hipMemcpyAsync(b->pin_index.p, b->d_index.p, 8 * iused, hipMemcpyDeviceToHost, b->stream));
     if(used) HIPCHK(hipMemcpyAsync(b->pin_out.p, b->d_pool.p, 4 * used, hipMemcpyDeviceToHost, b->stream));
     HIPCHK(hipStreamSynchronize(b->stream));
     const auto P3b = std::chrono::steady_clock::now();
-    if(n > 0) { memcpy(b->n_paths.data(), h_np, 4 * (size_t)n); memcpy(b->n_iters.data(), h_ni, 4 * (size_t)n); }
+    if(!ended) take_counters(b);
     b->res.ext_pool = (const uint32_t*)b->pin_out.p; b->res.ext_words = used;
     b->res.status = b->status; b->res.n_iters = b->n_iters;
     // paths AND transcripts of the batch, decoded, in host memory: every record is reached through the index the kernel wrote
@@ -622,17 +710,16 @@ int ald_batch_download(ald_batch *b)
         if(rc != 0) return set_err(ALD_ERR_STATE, "result index is inconsistent with the record pool (rc=" + std::to_string(rc) + ")");
         b->total_paths = b->res.n_paths();
     }
-    { auto ms = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point c) { return std::chrono::duration<double, std::milli>(c - a).count(); };
-      b->dl_ms[0] = ms(P0, P1); b->dl_ms[1] = ms(P1, P3); b->dl_ms[2] = ms(P3, P3b); b->dl_ms[3] = ms(P3b, std::chrono::steady_clock::now()); b->dl_bytes = 4 * (int64_t)used + 8 * (int64_t)iused + 20 * (int64_t)n; }
-    if(prof) { auto ms = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point c) { return std::chrono::duration<double, std::milli>(c - a).count(); };
-        fprintf(stderr, "[download] wait for the kernel %.2f ms, status copy %.2f ms, retries + counters %.2f ms, records + index (%.0f MB) + decode of %lld paths %.2f ms\n", ms(P0, P1), ms(P1, P2), ms(P2, P3), 4e-6 * (double)used + 8e-6 * (double)iused, (long long)b->total_paths, ms(P3, std::chrono::steady_clock::now())); }
+    b->dl_ms[0] = ms_between(P0, P1); b->dl_ms[1] = ms_between(P1, P3); b->dl_ms[2] = ms_between(P3, P3b); b->dl_ms[3] = ms_between(P3b, std::chrono::steady_clock::now()); b->dl_bytes = 4 * (int64_t)used + 8 * (int64_t)iused + 20 * (int64_t)n;
+    if(prof)
+        fprintf(stderr, "[download] wait for the kernel %.2f ms, status copy %.2f ms, retries + counters %.2f ms, records + index (%.0f MB) + decode of %lld paths %.2f ms\n", ms_between(P0, P1), ms_between(P1, P2), ms_between(P2, P3), 4e-6 * (double)used + 8e-6 * (double)iused, (long long)b->total_paths, ms_between(P3, std::chrono::steady_clock::now()));
     if(b->trace_cap > 0 && n > 0) {
         b->trace_n.resize(n); b->trace_codes.resize(3ull * n * b->trace_cap); b->trace_vals.resize((size_t)n * b->trace_cap);
         HIPCHK(hipMemcpy(b->trace_n.data(), b->d_trace_n.p, 4 * (size_t)n, hipMemcpyDeviceToHost));
         HIPCHK(hipMemcpy(b->trace_codes.data(), b->d_trace_codes.p, 12ull * n * b->trace_cap, hipMemcpyDeviceToHost));
         HIPCHK(hipMemcpy(b->trace_vals.data(), b->d_trace_vals.p, 8ull * n * b->trace_cap, hipMemcpyDeviceToHost));
     }
-    b->downloaded = true;
+    b->downloaded = true; b->finished = false;             // downloaded is the stronger state
     return ALD_OK;
 }
 

@@ -75,6 +75,12 @@ struct ald_batch {
     uint64_t pool_cap_words = 0;
     int trace_cap = 0;
     bool uploaded = false, ran = false, downloaded = false;
+    // ald_batch_finish: the run has ended on the device -- status words read, capacity retries and pool growth done, the per-graph counters on
+    // the host -- but no record has left HBM.  path_begin: row prefix of the (graph, path) order, as HostResults::path_begin after a download
+    bool finished = false;
+    std::vector<int64_t> path_begin;
+    uint64_t used_words = 0, used_index = 0;               // record words / index entries the run wrote (clamped to the capacities)
+    double fin_ms[2] = {0, 0}; int64_t fin_bytes = 0;      // last finish: waiting for the kernel / status + retries + counters; bytes moved to the host
     double kernel_ms = -1;
     // per-graph scheduling state
     std::vector<int32_t> cls, attempt, status, n_paths, n_iters;

@@ -262,7 +262,7 @@ int ald_batch_add_graph_raw(ald_batch *b, const ald_graph_view *g, const ald_pha
         delete S;
         return rc;
     }
-    b->uploaded = b->ran = b->downloaded = false;
+    b->uploaded = b->ran = b->downloaded = b->finished = false;
     int rc;
     try { rc = b->hb.add_graph_raw(*g, phases, max_group_boundary_distance); }
     catch(const std::bad_alloc &) { try { b->hb.clear(); } catch(...) {} return ald_set_err(ALD_ERR_NOMEM, "out of (pinned) host memory while staging: the batch was cleared"); }

@@ -1,4 +1,4 @@
-// trst_features.hip -- the transcript feature block of a whole downloaded batch (ald_batch_features_all): scallop::update_trst_features
+// trst_features.hip -- the transcript feature block of a whole downloaded or finished batch (ald_batch_features_all): scallop::update_trst_features
 // (scallop/scallop.cc:3268-3451) + unique_junc (:3472-3497), which the reference runs for every path it turns into a transcript
 // (scallop::build_transcripts, :3250-3266).
 //
@@ -36,14 +36,17 @@ int ald_batch_features_all_ex(ald_batch *b, const ald_batch_extras *x, uint32_t 
     if(!b) return ALD_ERR_INVALID;
     if(flags & ~ALD_FEAT_RAW_ON_DEVICE) return ald_set_err(ALD_ERR_INVALID, "ald_batch_features_all_ex: unknown flag bits");
     const bool raw_dev = (flags & ALD_FEAT_RAW_ON_DEVICE) != 0;
-    if(!b->downloaded) return ald_set_err(ALD_ERR_STATE, "ald_batch_features_all before ald_batch_download");
+    if(!b->downloaded && !b->finished) return ald_set_err(ALD_ERR_STATE, "ald_batch_features_all before ald_batch_download / ald_batch_finish");
+    // the host routine for raw graphs reads the downloaded records: a batch that is only finished has none
+    if(!b->downloaded && !raw_dev && b->hb.has_raw) return ald_set_err(ALD_ERR_STATE, "ald_batch_features_all: a finished batch that holds raw graphs needs ALD_FEAT_RAW_ON_DEVICE (or ald_batch_download)");
     const auto T0 = std::chrono::steady_clock::now();
     FeatTable &T = b->feat;
     T.valid = false; T.device_ms = 0; T.call_ms = 0; T.device_graphs = 0; T.host_graphs = 0;
     HCHK(hipSetDevice(b->device));
     const HostBatch &hb = b->hb; const int n = hb.n();
     const int64_t rows = b->total_paths;
-    T.row_begin.assign(b->res.path_begin.begin(), b->res.path_begin.end());
+    const std::vector<int64_t> &path_begin = b->downloaded ? b->res.path_begin : b->path_begin;
+    T.row_begin.assign(path_begin.begin(), path_begin.end());
     if(T.row_begin.empty()) T.row_begin.assign(1, 0);
     T.n_rows = rows;
     if(T.row_begin.back() != rows) return ald_set_err(ALD_ERR_STATE, "feature table: path table and path count disagree");
@@ -93,7 +96,7 @@ int ald_batch_features_all_ex(ald_batch *b, const ald_batch_extras *x, uint32_t 
             if(np > 0 && 2 * np + 2 * np * (V > 3 ? V - 3 : 0) > (int64_t)A.lds_words) need_scratch = true;
         }
         if(need_scratch) {
-            const uint64_t words = b->res.ext_words ? b->res.ext_words : b->pool_cap_words;
+            const uint64_t words = b->downloaded && b->res.ext_words ? b->res.ext_words : b->pool_cap_words;      // (a finished batch has no host pool: the capacity bounds it)
             if(T.d_scratch.ensure(8 * (size_t)words + 256)) return ald_set_err(ALD_ERR_NOMEM, "feature scratch");
             A.scratch = (int32_t*)T.d_scratch.p;
         }
@@ -169,7 +172,7 @@ int ald_batch_features_table(const ald_batch *b, const ald_trst_features **rows,
                              const int64_t **row_begin, int64_t *n_rows)
 {
     if(!b) return ALD_ERR_INVALID;
-    if(!b->downloaded || !b->feat.valid) return ald_set_err(ALD_ERR_STATE, "ald_batch_features_table without ald_batch_features_all on the last download");
+    if((!b->downloaded && !b->finished) || !b->feat.valid) return ald_set_err(ALD_ERR_STATE, "ald_batch_features_table without ald_batch_features_all on the last download");
     const FeatTable &T = b->feat;
     if(rows) *rows = (const ald_trst_features*)T.h_rows.p;
     if(complete) *complete = (const int32_t*)T.h_complete.p;
@@ -182,7 +185,7 @@ int ald_batch_features_table(const ald_batch *b, const ald_trst_features **rows,
 int ald_batch_features_stats(const ald_batch *b, double *device_ms, double *call_ms, int64_t *device_graphs, int64_t *host_graphs)
 {
     if(!b) return ALD_ERR_INVALID;
-    if(!b->downloaded || !b->feat.valid) return ald_set_err(ALD_ERR_STATE, "ald_batch_features_stats without ald_batch_features_all on the last download");
+    if((!b->downloaded && !b->finished) || !b->feat.valid) return ald_set_err(ALD_ERR_STATE, "ald_batch_features_stats without ald_batch_features_all on the last download");
     const FeatTable &T = b->feat;
     if(device_ms) *device_ms = T.device_ms;
     if(call_ms) *call_ms = T.call_ms;

@@ -26,11 +26,14 @@ struct TxSample { int32_t gid, sid, count1, pad; double cov2, conf, abd; };
 // scratch of a front end run (owned by a batch or a resident set and kept across calls, or temporary for the stream entry point)
 struct RedScratch { DevBuf *red; PinBuf *pin; hipStream_t st; };
 
-// What the front end leaves behind.  In S.red: [2] coverage per path, [6] sorted group keys, [7] sorted (group, sample) keys,
+// What the front end leaves behind.  In S.red: [2] coverage per path, [3] weight per path (tx_front_sort without h_cov), [6] sorted group keys, [7] sorted (group, sample) keys,
 // [8] path of every sorted position (sidx), [11] head flags, [12] 1-based group id of every sorted position, [13] TxGroup[n_groups],
 // [17] TxSample[n_runs] (sorted by group, then sample id).  host_paths: the transcripts with fewer than two exons, (graph, path) order.
 // ev0 (optional): recorded once the inputs are on the device, i.e. where the device time of the caller's section begins.
-struct TxFront { int64_t np = 0, n_dev = 0; int32_t n_groups = 0, n_runs = 0; std::vector<int64_t> host_paths; hipEvent_t ev0 = nullptr; bool sid_on_device = false; };
+// ev_w / h_cov: only when the coverages are made from the records (tx_front_sort without h_cov): the event behind the D2H of the weights,
+// and the coverages tx_front_coverage computed (pinned, S.pin[5]).
+struct TxFront { int64_t np = 0, n_dev = 0; int32_t n_groups = 0, n_runs = 0; std::vector<int64_t> host_paths; hipEvent_t ev0 = nullptr; bool sid_on_device = false;
+                 hipEvent_t ev_w = nullptr; const double *h_cov = nullptr; };
 inline const uint64_t *tx_skey(const RedScratch &S) { return (const uint64_t*)S.red[6].p; }
 inline const int64_t *tx_sidx(const RedScratch &S) { return (const int64_t*)S.red[8].p; }
 inline const int32_t *tx_head(const RedScratch &S) { return (const int32_t*)S.red[11].p; }
@@ -41,16 +44,30 @@ inline TxSample *tx_samples(const RedScratch &S) { return (TxSample*)S.red[17].p
 // exon join / bucket hash / stable sort by group / head flags / group ids: F.n_dev, F.n_groups, F.host_paths.  h_cov: coverage per path
 // (host libm), sid: sample per graph or null.  Enqueued on S.st; returns after the counts are on the host.
 int tx_front_groups(RedScratch S, TxIn in, const double *h_cov, int n_graphs, const int32_t *sid, TxFront &F);
+// tx_front_groups in its two halves, for a caller without a host copy of the records (a batch that ald_batch_finish ended):
+//   tx_front_sort      keys + the stable sort, ENQUEUED only.  h_cov = null: the key pass also writes weight[p] (record word 6) into a dense
+//                      array in (graph, path) order (S.red[3]), 8 bytes per path go to pinned memory (S.pin[4]) and F.ev_w is recorded
+//   tx_front_coverage  waits for F.ev_w, takes log(1 + w) with the host's libm on up to 16 threads (ALD_SINK_THREADS) WHILE THE SORT RUNS, and
+//                      enqueues the upload to where tx_front_groups puts h_cov (S.red[2]): coverage is first read by tx_fold
+//   tx_front_heads     waits for the sort; head flags, group ids, F.n_dev / n_groups / host_paths
+int tx_front_sort(RedScratch S, TxIn in, const double *h_cov, int n_graphs, const int32_t *sid, TxFront &F);
+int tx_front_coverage(RedScratch S, TxFront &F);
+int tx_front_heads(RedScratch S, TxIn in, TxFront &F);
+// The records of F.host_paths (fewer than two exons) compacted on the device -- lengths, exclusive scan, a 16-lane copy per record into
+// d_out -- and brought to pinned memory (S.pin[6]: offsets, S.pin[7]: words): *h_words + (*h_off)[a] is the record of F.host_paths[a].
+// Enqueued on S.st; the caller waits for the stream before it reads them.
+int tx_compact_singles(RedScratch S, TxIn in, const TxFront &F, DevBuf &d_out, const uint32_t **h_words, const unsigned long long **h_off);
 // the fold of every group (tx_fold) and its per-sample runs (tx_sfold).  start_idx[group] >= 0: the group lands on a resident item whose
 // coverage start_cov[start_idx[group]] the group's graphs add to, one by one ((c + s1) + s2) + ...; null: every group starts empty.
 int tx_front_fold(RedScratch S, TxIn in, TxFront &F, const int64_t *start_idx, const double *start_cov);
 // the transcripts with fewer than two exons into `into`, graph by graph (one per-graph set per graph, assembler.cc:1105-1133)
+// h_off (optional): the record of host_paths[a] lies at h_pool + h_off[a] (tx_compact_singles) instead of h_pool + h_roff[host_paths[a]]
 void tx_host_singles(aletsch::transcript_sink &into, const std::vector<int64_t> &host_paths, const uint32_t *h_pool, const unsigned long long *h_roff,
-                     const double *h_cov, const int64_t *h_tid, const int32_t *sid, const int64_t *label, int64_t tid_base);
+                     const double *h_cov, const int64_t *h_tid, const int32_t *sid, const int64_t *label, int64_t tid_base, const unsigned long long *h_off = nullptr);
 // a transcript stream (format of ald_batch_transcript_stream) turned into records the front end reads
 struct StreamRecords { std::vector<uint32_t> pool; std::vector<unsigned long long> roff; std::vector<double> cov; std::vector<int32_t> sid; std::vector<int64_t> label, tids; };
 int tx_stream_records(const uint32_t *words, int64_t n_words, const double *coverage, const int64_t *tid, int32_t skip_single_exon, int64_t graph_offset, StreamRecords &R);
-// a downloaded batch's path table in (graph, path) order on the device (b->d_ordoff), built once per download
+// the path table of a downloaded or finished batch in (graph, path) order on the device (b->d_ordoff), built once per run
 int device_path_table(ald_batch *b);
 
 // the reduced set of one batch, flat, in the reference's iteration order (ascending bucket hash, bucket order inside)

@@ -48,7 +48,9 @@ __host__ __device__ inline uint64_t chain_key_dev(const int32_t *x, int n_words)
     return (h & 0x7FFFFFFFull) + 1;
 }
 
-__global__ void tx_build(TxIn in, int32_t *nwords, uint64_t *key, int32_t *graph_of)
+// WEIGHT: also weight[p] = the record's weight (word 6), dense in (graph, path) order -- consecutive lanes write consecutive doubles -- for a
+// caller that has no host copy of the records and takes coverage = log(1 + weight) on the host (tx_front_coverage)
+template<bool WEIGHT> __global__ void tx_build(TxIn in, int32_t *nwords, uint64_t *key, int32_t *graph_of, double *weight)
 {
     const int64_t p = (int64_t)blockIdx.x * TX_BLOCK + threadIdx.x;
     if(p >= in.np) return;
@@ -56,6 +58,7 @@ __global__ void tx_build(TxIn in, int32_t *nwords, uint64_t *key, int32_t *graph
     const int g = (int)r[0], k = (int)r[REC_NEXW]; const int strand = (int)(r[5] & 0xFF);
     const int32_t *ex = rec_exons(r);
     nwords[p] = k; graph_of[p] = g;
+    if(WEIGHT) { double w; memcpy(&w, r + 6, 8); weight[p] = w; }
     if(k <= 2) { key[p] = TX_HOST; return; }
     const uint64_t bucket = chain_key_dev(ex, k);
     // group = (bucket, exons, strand, the words compare1 looks at: 1, 2 .. k-5, k-2); 32 bits of it ride in the sort key
@@ -177,9 +180,28 @@ __global__ void ts_emit(TxIn in, const int64_t *at, const int32_t *sid, uint32_t
     for(int q = l; q < k; q += 16) w[ALD_TS_HDR + q] = x[q];
 }
 
+// ---- the records of the transcripts the host merges (fewer than two exons), compacted: hp[a] = path of the a-th of them
+__global__ void sx_len(TxIn in, const int64_t *hp, int64_t ns, int64_t *len)
+{
+    const int64_t a = (int64_t)blockIdx.x * TX_BLOCK + threadIdx.x;
+    if(a > ns) return;
+    if(a == ns) { len[a] = 0; return; }                   // (the exclusive scan over ns + 1 entries leaves the total in the last one)
+    const uint32_t *r = in.pool + in.roff[hp[a]];
+    len[a] = (int64_t)rec_words(r[2], r[REC_NEXW]);       // header + vertices + exon words, padded to even
+}
+// one 16-lane group per record, consecutive lanes on consecutive words (as ts_emit copies)
+__global__ void sx_copy(TxIn in, const int64_t *hp, const int64_t *at, int64_t ns, uint32_t *out)
+{
+    const int64_t a = ((int64_t)blockIdx.x * TX_BLOCK + threadIdx.x) / 16; const int l = (int)(threadIdx.x & 15);
+    if(a >= ns) return;
+    const uint32_t *r = in.pool + in.roff[hp[a]];
+    const int64_t o = at[a], w = at[a + 1] - o;
+    for(int64_t q = l; q < w; q += 16) out[o + q] = r[q];
+}
+
 } // namespace
 
-// The result index of a downloaded batch in (graph, path) order, in DEVICE memory: d_ordoff[path_begin[g] + p] = pool offset of record
+// The result index of a downloaded or finished batch in (graph, path) order, in DEVICE memory: d_ordoff[path_begin[g] + p] = pool offset of record
 // (g, p).  Everything comes from what the decomposition kernel left in HBM -- the per-graph path counts, graph_first and the index
 // entries -- so the transcript stream and the set reduction start without any host-side table.
 int device_path_table(ald_batch *b)
@@ -201,23 +223,29 @@ int device_path_table(ald_batch *b)
     return ALD_OK;
 }
 
-int tx_front_groups(RedScratch S, TxIn in, const double *h_cov, int n_graphs, const int32_t *sid, TxFront &F)
+int tx_front_sort(RedScratch S, TxIn in, const double *h_cov, int n_graphs, const int32_t *sid, TxFront &F)
 {
     const int64_t np = in.np;
-    F.np = np; F.n_dev = 0; F.n_groups = 0; F.n_runs = 0; F.host_paths.clear(); F.sid_on_device = sid != nullptr;
+    F.np = np; F.n_dev = 0; F.n_groups = 0; F.n_runs = 0; F.host_paths.clear(); F.sid_on_device = sid != nullptr; F.h_cov = nullptr;
     if(np == 0) { if(F.ev0) HCHK(hipEventRecord(F.ev0, S.st)); return ALD_OK; }
-    DevBuf &d_cov = S.red[2], &d_nw = S.red[4], &d_key = S.red[5], &d_key2 = S.red[6], &d_idx = S.red[7], &d_idx2 = S.red[8], &d_graph = S.red[9],
+    DevBuf &d_cov = S.red[2], &d_w = S.red[3], &d_nw = S.red[4], &d_key = S.red[5], &d_key2 = S.red[6], &d_idx = S.red[7], &d_idx2 = S.red[8], &d_graph = S.red[9],
            &d_sid = S.red[10], &d_head = S.red[11], &d_gid = S.red[12], &d_tmp = S.red[14], &d_head2 = S.red[15], &d_rid = S.red[16], &d_pos = S.red[18], &d_pos2 = S.red[19];
-    PinBuf &p_key = S.pin[0];
-    if(p_key.ensure(8 * (size_t)np, true)) return ald_set_err(ALD_ERR_NOMEM, "pinned reduction buffers");
-    if(d_cov.ensure(8 * (size_t)np) || d_nw.ensure(4 * (size_t)np) || d_key.ensure(8 * (size_t)np)
+    PinBuf &p_key = S.pin[0], &p_w = S.pin[4], &p_cov = S.pin[5];
+    const bool from_records = h_cov == nullptr;
+    if(from_records && !F.ev_w) return ald_set_err(ALD_ERR_INVALID, "tx_front_sort: coverage from the records needs an event");
+    if(p_key.ensure(8 * (size_t)np, true) || (from_records && (p_w.ensure(8 * (size_t)np, true) || p_cov.ensure(8 * (size_t)np)))) return ald_set_err(ALD_ERR_NOMEM, "pinned reduction buffers");
+    if(d_cov.ensure(8 * (size_t)np) || d_nw.ensure(4 * (size_t)np) || d_key.ensure(8 * (size_t)np) || (from_records && d_w.ensure(8 * (size_t)np))
        || d_key2.ensure(8 * (size_t)np) || d_idx.ensure(8 * (size_t)np) || d_idx2.ensure(8 * (size_t)np) || d_graph.ensure(4 * (size_t)np) || d_head.ensure(4 * (size_t)np) || d_gid.ensure(4 * (size_t)np)
        || d_head2.ensure(4 * (size_t)np) || d_rid.ensure(4 * (size_t)np) || d_pos.ensure(8 * (size_t)np) || d_pos2.ensure(8 * (size_t)np) || (sid && d_sid.ensure(4 * (size_t)n_graphs + 4))) return ald_set_err(ALD_ERR_NOMEM, "reduction buffers");
     hipStream_t st = S.st;
-    HCHK(hipMemcpyAsync(d_cov.p, h_cov, 8 * (size_t)np, hipMemcpyHostToDevice, st));
+    if(!from_records) HCHK(hipMemcpyAsync(d_cov.p, h_cov, 8 * (size_t)np, hipMemcpyHostToDevice, st));
     if(sid) HCHK(hipMemcpyAsync(d_sid.p, sid, 4 * (size_t)n_graphs, hipMemcpyHostToDevice, st));
     if(F.ev0) HCHK(hipEventRecord(F.ev0, st));
-    hipLaunchKernelGGL(tx_build, dim3(grid_for(np)), dim3(TX_BLOCK), 0, st, in, (int32_t*)d_nw.p, (uint64_t*)d_key.p, (int32_t*)d_graph.p);
+    if(from_records) {
+        hipLaunchKernelGGL(tx_build<true>, dim3(grid_for(np)), dim3(TX_BLOCK), 0, st, in, (int32_t*)d_nw.p, (uint64_t*)d_key.p, (int32_t*)d_graph.p, (double*)d_w.p);
+        HCHK(hipMemcpyAsync(p_w.p, d_w.p, 8 * (size_t)np, hipMemcpyDeviceToHost, st));
+        HCHK(hipEventRecord(F.ev_w, st));
+    } else hipLaunchKernelGGL(tx_build<false>, dim3(grid_for(np)), dim3(TX_BLOCK), 0, st, in, (int32_t*)d_nw.p, (uint64_t*)d_key.p, (int32_t*)d_graph.p, (double*)nullptr);
     hipLaunchKernelGGL(tx_iota, dim3(grid_for(np)), dim3(TX_BLOCK), 0, st, (int64_t*)d_idx.p, np);
     // stable sort by group key: members of a group stay in (graph, path) order; host-side transcripts (key = ~0) sink to the end
     size_t tmp_bytes = 0;
@@ -226,13 +254,37 @@ int tx_front_groups(RedScratch S, TxIn in, const double *h_cov, int n_graphs, co
     HCHK(hipcub::DeviceScan::InclusiveSum(nullptr, scan_bytes, (const int32_t*)d_head.p, (int32_t*)d_gid.p, (int)np, st));
     if(d_tmp.ensure(std::max(tmp_bytes, scan_bytes) + 256)) return ald_set_err(ALD_ERR_NOMEM, "sort scratch");
     HCHK(hipcub::DeviceRadixSort::SortPairs(d_tmp.p, tmp_bytes, (const uint64_t*)d_key.p, (uint64_t*)d_key2.p, (const int64_t*)d_idx.p, (int64_t*)d_idx2.p, (int)np, 0, 64, st));
-    // how many went to the device: the sorted keys below TX_HOST
-    const uint64_t *h_key = (const uint64_t*)p_key.p;
+    // how many went to the device: the sorted keys below TX_HOST (tx_front_heads looks)
     HCHK(hipMemcpyAsync(p_key.p, d_key2.p, 8 * (size_t)np, hipMemcpyDeviceToHost, st));
+    return ALD_OK;
+}
+
+int tx_front_coverage(RedScratch S, TxFront &F)
+{
+    const int64_t np = F.np;
+    if(np == 0) return ALD_OK;
+    HCHK(hipEventSynchronize(F.ev_w));                     // the weights are in pinned memory; the sort is running
+    const double *w = (const double*)S.pin[4].p; double *cov = (double*)S.pin[5].p;
+    const unsigned nthr = ald_sink_threads(np);
+    HostBatch::run_threads(nthr, [&](unsigned th) { for(int64_t i = np * th / nthr; i < np * (th + 1) / nthr; i++) cov[(size_t)i] = log(1.0 + w[(size_t)i]); });      // essential.cc:725, host libm
+    HCHK(hipMemcpyAsync(S.red[2].p, cov, 8 * (size_t)np, hipMemcpyHostToDevice, S.st));
+    F.h_cov = cov;
+    return ALD_OK;
+}
+
+int tx_front_heads(RedScratch S, TxIn in, TxFront &F)
+{
+    const int64_t np = F.np;
+    if(np == 0) return ALD_OK;
+    DevBuf &d_key2 = S.red[6], &d_idx2 = S.red[8], &d_head = S.red[11], &d_gid = S.red[12], &d_tmp = S.red[14];
+    hipStream_t st = S.st;
+    const uint64_t *h_key = (const uint64_t*)S.pin[0].p;
     HCHK(hipStreamSynchronize(st));
     const int64_t n_dev = (int64_t)(std::lower_bound(h_key, h_key + np, TX_HOST) - h_key);
     F.n_dev = n_dev;
     if(n_dev > 0) {
+        size_t scan_bytes = 0;
+        HCHK(hipcub::DeviceScan::InclusiveSum(nullptr, scan_bytes, (const int32_t*)d_head.p, (int32_t*)d_gid.p, (int)np, st));      // (d_tmp holds at least this: tx_front_sort)
         hipLaunchKernelGGL(tx_heads, dim3(grid_for(n_dev)), dim3(TX_BLOCK), 0, st, in, (const uint64_t*)d_key2.p, (const int64_t*)d_idx2.p, n_dev, (int32_t*)d_head.p);
         HCHK(hipcub::DeviceScan::InclusiveSum(d_tmp.p, scan_bytes, (const int32_t*)d_head.p, (int32_t*)d_gid.p, (int)n_dev, st));
         HCHK(hipMemcpyAsync(&F.n_groups, (int32_t*)d_gid.p + (n_dev - 1), 4, hipMemcpyDeviceToHost, st));
@@ -242,6 +294,39 @@ int tx_front_groups(RedScratch S, TxIn in, const double *h_cov, int n_graphs, co
     if(np > n_dev) HCHK(hipMemcpyAsync(F.host_paths.data(), (const int64_t*)d_idx2.p + n_dev, 8 * (size_t)(np - n_dev), hipMemcpyDeviceToHost, st));
     HCHK(hipStreamSynchronize(st));
     if(hipGetLastError() != hipSuccess) return ald_set_err(ALD_ERR_HIP, "a reduction kernel failed to launch");
+    return ALD_OK;
+}
+
+int tx_front_groups(RedScratch S, TxIn in, const double *h_cov, int n_graphs, const int32_t *sid, TxFront &F)
+{
+    if(!h_cov && in.np > 0) return ald_set_err(ALD_ERR_INVALID, "tx_front_groups: no coverages");
+    { int rc = tx_front_sort(S, in, h_cov, n_graphs, sid, F); if(rc != ALD_OK) return rc; }
+    return tx_front_heads(S, in, F);
+}
+
+int tx_compact_singles(RedScratch S, TxIn in, const TxFront &F, DevBuf &d_out, const uint32_t **h_words, const unsigned long long **h_off)
+{
+    const int64_t ns = (int64_t)F.host_paths.size();
+    *h_words = nullptr; *h_off = nullptr;
+    if(ns == 0) return ALD_OK;
+    DevBuf &d_len = S.red[0], &d_at = S.red[1], &d_tmp = S.red[14];
+    PinBuf &p_off = S.pin[6], &p_words = S.pin[7];
+    hipStream_t st = S.st;
+    const int64_t *hp = tx_sidx(S) + F.n_dev;             // the tail of the sorted order, still on the device
+    if(d_len.ensure(8 * (size_t)(ns + 1)) || d_at.ensure(8 * (size_t)(ns + 1)) || p_off.ensure(8 * (size_t)(ns + 1), true)) return ald_set_err(ALD_ERR_NOMEM, "single-exon compaction");
+    hipLaunchKernelGGL(sx_len, dim3(grid_for(ns + 1)), dim3(TX_BLOCK), 0, st, in, hp, ns, (int64_t*)d_len.p);
+    size_t scan_bytes = 0;
+    HCHK(hipcub::DeviceScan::ExclusiveSum(nullptr, scan_bytes, (const int64_t*)d_len.p, (int64_t*)d_at.p, (int)(ns + 1), st));
+    if(d_tmp.ensure(scan_bytes + 256)) return ald_set_err(ALD_ERR_NOMEM, "scan scratch");
+    HCHK(hipcub::DeviceScan::ExclusiveSum(d_tmp.p, scan_bytes, (const int64_t*)d_len.p, (int64_t*)d_at.p, (int)(ns + 1), st));
+    HCHK(hipMemcpyAsync(p_off.p, d_at.p, 8 * (size_t)(ns + 1), hipMemcpyDeviceToHost, st));
+    HCHK(hipStreamSynchronize(st));
+    const int64_t total = ((const int64_t*)p_off.p)[ns];
+    if(total < 0 || d_out.ensure(4 * (size_t)total + 64) || p_words.ensure(4 * (size_t)total + 64, true)) return ald_set_err(ALD_ERR_NOMEM, "single-exon records");
+    hipLaunchKernelGGL(sx_copy, dim3(grid_for(16 * ns)), dim3(TX_BLOCK), 0, st, in, hp, (const int64_t*)d_at.p, ns, (uint32_t*)d_out.p);
+    if(hipGetLastError() != hipSuccess) return ald_set_err(ALD_ERR_HIP, "a compaction kernel failed to launch");
+    if(total) HCHK(hipMemcpyAsync(p_words.p, d_out.p, 4 * (size_t)total, hipMemcpyDeviceToHost, st));
+    *h_words = (const uint32_t*)p_words.p; *h_off = (const unsigned long long*)p_off.p;
     return ALD_OK;
 }
 
@@ -275,24 +360,26 @@ int tx_front_fold(RedScratch S, TxIn in, TxFront &F, const int64_t *start_idx, c
 }
 
 void tx_host_singles(aletsch::transcript_sink &into, const std::vector<int64_t> &host_paths, const uint32_t *h_pool, const unsigned long long *h_roff,
-                     const double *h_cov, const int64_t *h_tid, const int32_t *sid, const int64_t *label, int64_t tid_base)
+                     const double *h_cov, const int64_t *h_tid, const int32_t *sid, const int64_t *label, int64_t tid_base, const unsigned long long *h_off)
 {
     // one without any exon lands in bucket 0, as get_intron_chain_hashing puts it
     aletsch::sink_transcript x;
-    auto fill = [&](int64_t p) {
-        const uint32_t *r = h_pool + h_roff[(size_t)p]; const int g = (int)r[0];
+    auto rec_at = [&](size_t a) { return h_off ? h_pool + h_off[a] : h_pool + h_roff[(size_t)host_paths[a]]; };
+    auto fill = [&](size_t a) {
+        const int64_t p = host_paths[a];
+        const uint32_t *r = rec_at(a); const int g = (int)r[0];
         double conf, abd; memcpy(&abd, r + 8, 8); memcpy(&conf, r + 10, 8);
         x.strand = (char)(r[5] & 0xFF); x.coverage = h_cov[(size_t)p]; x.top.cov2 = x.coverage; x.top.conf = conf; x.top.abd = abd; x.top.count1 = (int32_t)r[4]; x.count2 = 1;
         x.tid = h_tid ? h_tid[(size_t)p] : tid_base + (((label ? label[g] : (int64_t)g) << 20) | (int64_t)r[1]);
         const int32_t *ex = rec_exons(r); x.xs.assign(ex, ex + r[REC_NEXW]);
     };
     for(size_t a = 0; a < host_paths.size(); ) {          // one per-graph set per graph that has any (assembler.cc:1105-1133)
-        const int g = (int)h_pool[h_roff[(size_t)host_paths[a]]];
-        size_t e = a; while(e < host_paths.size() && (int)h_pool[h_roff[(size_t)host_paths[e]]] == g) e++;
-        if(e - a == 1) { fill(host_paths[a]); into.add(x, 1, sid ? sid[g] : -1); }   // merging a one-item set is the same as adding the item (transcript_set.cc:149-175)
+        const int g = (int)rec_at(a)[0];
+        size_t e = a; while(e < host_paths.size() && (int)rec_at(e)[0] == g) e++;
+        if(e - a == 1) { fill(a); into.add(x, 1, sid ? sid[g] : -1); }   // merging a one-item set is the same as adding the item (transcript_set.cc:149-175)
         else {
             aletsch::transcript_sink ts(into.single_exon_overlap());
-            for(size_t q = a; q < e; q++) { fill(host_paths[q]); ts.add(x, 1, sid ? sid[g] : -1); }
+            for(size_t q = a; q < e; q++) { fill(q); ts.add(x, 1, sid ? sid[g] : -1); }
             into.add(ts);
         }
         a = e;
@@ -487,7 +574,7 @@ int ald_tset_reduce_stream(int32_t device, const uint32_t *words, int64_t n_word
 int ald_batch_device_transcript_stream(const ald_batch *cb, const int32_t *sid, int32_t skip_single_exon, void **dev_words, int64_t *n_words)
 {
     if(!cb || !dev_words || !n_words) return ALD_ERR_INVALID;
-    if(!cb->downloaded) return ald_set_err(ALD_ERR_STATE, "ald_batch_device_transcript_stream before ald_batch_download");
+    if(!cb->downloaded && !cb->finished) return ald_set_err(ALD_ERR_STATE, "ald_batch_device_transcript_stream before ald_batch_download / ald_batch_finish");
     ald_batch *b = const_cast<ald_batch*>(cb);
     HCHK(hipSetDevice(b->device));
     const int n = b->hb.n(); const int64_t np = b->total_paths;

@@ -20,6 +20,9 @@
 //   rs_mark / scans / rs_slots   merge path: resident i -> i + #new before it, new j -> insertion point + #new before j
 //   rs_sizes / scans / rs_write  exon and sample counts per output item, prefix sums, then one gather pass into the other buffer set
 // ald_tset_dev_merge runs the same merge path with a second resident set as the incoming side (coverage c_dst + c_src).
+// A batch that ald_batch_finish ended has no host copy of its records: the front end then runs in its halves (tset_front.h: tx_front_sort /
+// _coverage / _heads) -- the key pass also writes the weights, the host takes log(1 + w) under the sort -- and the single-exon records
+// the host part merges are compacted on the device (tx_compact_singles).
 #include "tset_front.h"
 #include <hipcub/hipcub.hpp>
 #include <algorithm>
@@ -263,10 +266,11 @@ __global__ void rs_sbeg(const TxSample *smp, int64_t n_runs, int64_t n_groups, i
 
 struct ald_tset_dev {
     int device = 0; hipStream_t st = nullptr; hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    hipEvent_t ev_w = nullptr;                              // behind the D2H of a finished batch's weights (tx_front_sort)
     SetBufs buf[2]; int cur = 0;
     aletsch::transcript_sink single;                        // transcripts with fewer than two exons, in call order
     DevBuf red[20], d_pool, d_roff, d_label, d_tid; PinBuf pin[8];          // front end scratch (the set's own, never a batch's)
-    DevBuf w[16];                                           // merge-path scratch
+    DevBuf w[16];                                           // merge-path scratch ([14]: the compacted single-exon records of a finished batch)
     double last_device_ms = 0, last_call_ms = 0;
     explicit ald_tset_dev(double ov) : single(ov) {}
     SetBufs &res() { return buf[cur]; }
@@ -275,7 +279,7 @@ struct ald_tset_dev {
         for(auto &b : buf) b.release();
         for(auto &d : red) d.release(); for(auto &d : w) d.release(); for(auto &p : pin) p.release();
         d_pool.release(); d_roff.release(); d_label.release(); d_tid.release();
-        if(ev0) hipEventDestroy(ev0); if(ev1) hipEventDestroy(ev1);
+        if(ev0) hipEventDestroy(ev0); if(ev1) hipEventDestroy(ev1); if(ev_w) hipEventDestroy(ev_w);
         if(st) hipStreamDestroy(st);
     }
 };
@@ -330,6 +334,9 @@ template<class In> int merge_path(ald_tset_dev *s, In B, const int64_t *match, c
 
 // One batch (or stream) of records into the set.  d_pool / d_roff: records in (graph, path) order on the device; h_pool / h_roff / h_cov:
 // the same on the host (the single-exon part is merged there); label / h_tid as in tset_reduce.hip's reduce_core.
+// h_pool = null (a batch that ald_batch_finish ended: its records never left HBM): the two things the host part needs are fetched here --
+// the weights, 8 bytes per path, for coverage = log(1 + weight) with the host's libm, under the sort; and, unless skip_single_exon, the
+// records of the transcripts with fewer than two exons, compacted on the device.
 int add_records(ald_tset_dev *s, const uint32_t *d_pool, const unsigned long long *d_roff, const uint32_t *h_pool, const unsigned long long *h_roff, const double *h_cov,
                 const int64_t *h_tid, int64_t np, int n_graphs, const int32_t *sid, const int64_t *label, int64_t tid_base, int32_t skip_single_exon)
 {
@@ -339,7 +346,16 @@ int add_records(ald_tset_dev *s, const uint32_t *d_pool, const unsigned long lon
     RedScratch S; S.red = s->red; S.pin = s->pin; S.st = st;
     TxIn in; in.roff = d_roff; in.pool = d_pool; in.np = np;
     TxFront X; X.ev0 = s->ev0;
-    { int rc = tx_front_groups(S, in, h_cov, n_graphs, sid, X); if(rc != ALD_OK) return rc; }
+    const unsigned long long *h_off = nullptr;             // != null: h_pool holds the single-exon records only, in the order of X.host_paths
+    if(h_pool) { int rc = tx_front_groups(S, in, h_cov, n_graphs, sid, X); if(rc != ALD_OK) return rc; }
+    else {
+        X.ev_w = s->ev_w;
+        { int rc = tx_front_sort(S, in, nullptr, n_graphs, sid, X); if(rc != ALD_OK) return rc; }
+        { int rc = tx_front_coverage(S, X); if(rc != ALD_OK) return rc; }
+        { int rc = tx_front_heads(S, in, X); if(rc != ALD_OK) return rc; }
+        h_cov = X.h_cov; h_roff = nullptr;
+        if(!skip_single_exon) { int rc = tx_compact_singles(S, in, X, s->w[14], &h_pool, &h_off); if(rc != ALD_OK) return rc; }      // read behind the stream waits below
+    }
     if(X.n_groups > 0) {
         const int64_t G = X.n_groups;
         DevBuf &d_ghead = s->w[0], &d_perm = s->w[1], &d_match = s->w[2], &d_ins = s->w[3], &d_unm = s->w[4], &d_start = s->w[5], &d_sbeg = s->w[13], &d_lab = s->d_label, &d_ptid = s->d_tid;
@@ -365,7 +381,7 @@ int add_records(ald_tset_dev *s, const uint32_t *d_pool, const unsigned long lon
     }
     float ms = 0; if(hipEventElapsedTime(&ms, s->ev0, s->ev1) == hipSuccess) s->last_device_ms = ms;
     // the device part is in: the transcripts with fewer than two exons, graph by graph, into the host part
-    if(!skip_single_exon) tx_host_singles(s->single, X.host_paths, h_pool, h_roff, h_cov, h_tid, sid, label, tid_base);
+    if(!skip_single_exon) tx_host_singles(s->single, X.host_paths, h_pool, h_roff, h_cov, h_tid, sid, label, tid_base, h_off);
     return ALD_OK;
 }
 
@@ -454,7 +470,7 @@ int ald_tset_dev_create(int32_t device, double single_exon_overlap, ald_tset_dev
     std::unique_ptr<ald_tset_dev> s(new ald_tset_dev(single_exon_overlap));
     s->device = device;
     HCHK(hipStreamCreateWithFlags(&s->st, hipStreamNonBlocking));
-    HCHK(hipEventCreate(&s->ev0)); HCHK(hipEventCreate(&s->ev1));
+    HCHK(hipEventCreate(&s->ev0)); HCHK(hipEventCreate(&s->ev1)); HCHK(hipEventCreateWithFlags(&s->ev_w, hipEventDisableTiming));
     *out = s.release();
     return ALD_OK;
 }
@@ -472,14 +488,15 @@ int ald_tset_dev_add_batch(ald_tset_dev *s, const ald_batch *cb, const int32_t *
 {
     if(!s || !cb) return ALD_ERR_INVALID;
     if(cb->device != s->device) return ald_set_err(ALD_ERR_INVALID, "ald_tset_dev_add_batch: the batch lives on another device");
-    if(!cb->downloaded) return ald_set_err(ALD_ERR_STATE, "ald_tset_dev_add_batch before ald_batch_download");
+    if(!cb->downloaded && !cb->finished) return ald_set_err(ALD_ERR_STATE, "ald_tset_dev_add_batch before ald_batch_download / ald_batch_finish");
     const auto T0 = std::chrono::steady_clock::now();
     ald_batch *b = const_cast<ald_batch*>(cb);
     HCHK(hipSetDevice(s->device));
     { int rc = device_path_table(b); if(rc != ALD_OK) return rc; }
     HCHK(hipStreamSynchronize(b->stream));                 // the path table is built on the batch's stream; everything else runs on the set's
-    const int rc = add_records(s, (const uint32_t*)b->d_pool.p, (const unsigned long long*)b->d_ordoff.p, b->res.pool_data(), (const unsigned long long*)b->res.rec_off.data(),
-                               b->res.coverage.data(), nullptr, b->total_paths, b->hb.n(), sid, nullptr, tid_base, skip_single_exon);
+    const bool host = b->downloaded;                        // a batch that is only finished has no host copy of its records
+    const int rc = add_records(s, (const uint32_t*)b->d_pool.p, (const unsigned long long*)b->d_ordoff.p, host ? b->res.pool_data() : nullptr, host ? (const unsigned long long*)b->res.rec_off.data() : nullptr,
+                               host ? b->res.coverage.data() : nullptr, nullptr, b->total_paths, b->hb.n(), sid, nullptr, tid_base, skip_single_exon);
     s->last_call_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - T0).count();
     return rc;
 }

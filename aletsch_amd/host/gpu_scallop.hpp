@@ -189,13 +189,28 @@ public:
         return (int)lpos_.size() - 1;
     }
     void flush() {
-        int rc;
+        int rc; status_.clear();
         if((rc = ald_batch_upload(b_)) != ALD_OK) throw gpu_error(rc, "ald_batch_upload");
         if((rc = ald_batch_run(b_)) != ALD_OK) throw gpu_error(rc, "ald_batch_run");
         if((rc = ald_batch_download(b_)) != ALD_OK) throw gpu_error(rc, "ald_batch_download");
     }
+    // upload, run and END the run on the device (ald_batch_finish): the records stay in HBM.  For a caller whose consumers read them there --
+    // ald_tset_dev_add_batch(set, handle(), ...), ald_batch_device_transcript_stream, features() -- and who does not read paths(); status(i)
+    // works after either flush, paths(i) needs flush() (or ald_batch_download(handle()) afterwards, which then only fetches the records).
+    void flush_on_device() {
+        int rc;
+        if((rc = ald_batch_upload(b_)) != ALD_OK) throw gpu_error(rc, "ald_batch_upload");
+        if((rc = ald_batch_run(b_)) != ALD_OK) throw gpu_error(rc, "ald_batch_run");
+        if((rc = ald_batch_finish(b_)) != ALD_OK) throw gpu_error(rc, "ald_batch_finish");
+        status_.assign(lpos_.size(), -1);
+        if(!status_.empty() && (rc = ald_batch_export_status(b_, status_.data(), nullptr, nullptr)) != ALD_OK) throw gpu_error(rc, "ald_batch_export_status");
+    }
     // per-graph status word (ALD_ST_*): the reference would have aborted on an assert where this is >= ALD_ST_INVARIANT
-    int status(int i) const { ald_result_view r; if(ald_batch_get_result(b_, i, &r) != ALD_OK) return -1; return r.status; }
+    int status(int i) const {
+        ald_result_view r;
+        if(ald_batch_get_result(b_, i, &r) == ALD_OK) return r.status;
+        return i >= 0 && i < (int)status_.size() ? (int)status_[(size_t)i] : -1;      // after flush_on_device()
+    }
     std::vector<Path> paths(int i) const {
         ald_result_view r;
         int rc = ald_batch_get_result(b_, i, &r);
@@ -204,7 +219,7 @@ public:
         for(int k = 0; k < r.num_paths; k++) { ald_path_view pv; ald_batch_get_path(b_, i, k, &pv); out.push_back(make_path<Path>(pv, lpos_[i], rpos_[i])); }
         return out;
     }
-    void clear() { ald_batch_clear(b_); lpos_.clear(); rpos_.clear(); extras_.clear(); }
+    void clear() { ald_batch_clear(b_); lpos_.clear(); rpos_.clear(); extras_.clear(); status_.clear(); }
     ald_batch *handle() const { return b_; }        // for the calls that take the batch itself (ald_tset_add_batch, ald_batch_export_transcripts, ...)
 
     // ---- the transcript feature block (scallop::update_trst_features, scallop.cc:3268-3451), opt-in.  Member templates: instantiated only
@@ -297,6 +312,7 @@ private:
     ald_batch *b_ = nullptr;
     bool feat_raw_on_device_ = false;
     std::vector<std::vector<int32_t>> lpos_, rpos_;
+    std::vector<int32_t> status_;                   // per ticket, after flush_on_device()
     std::vector<graph_extras> extras_;              // per ticket, filled by the *_with_extras forms only
 };
 

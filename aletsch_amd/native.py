@@ -230,8 +230,10 @@ def load_library():
     lib.ald_batch_last_kernel_ms.restype = C.c_double
     lib.ald_batch_last_kernel_ms.argtypes = [C.c_void_p]
     for name in ("ald_batch_destroy", "ald_batch_clear", "ald_batch_upload", "ald_batch_run", "ald_batch_sync",
-                 "ald_batch_download", "ald_batch_num_graphs"):
+                 "ald_batch_download", "ald_batch_finish", "ald_batch_num_graphs"):
         getattr(lib, name).argtypes = [C.c_void_p]
+    lib.ald_batch_export_status.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.ald_batch_last_finish_ms.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int64)]
     lib.ald_batch_result_index.argtypes = [C.c_void_p, C.POINTER(C.POINTER(C.c_uint64)), C.POINTER(C.c_int64), C.POINTER(C.POINTER(C.c_int64))]
     lib.ald_batch_last_download_ms.argtypes = [C.c_void_p] + [C.POINTER(C.c_double)] * 4 + [C.POINTER(C.c_int64)]
     lib.ald_batch_enable_trace.argtypes = [C.c_void_p, C.c_int32]
@@ -389,6 +391,24 @@ class DecompBatch:
 
     def download(self):
         _check(self._lib.ald_batch_download(self._h))
+
+    def finish(self):
+        """End the run on the device (ald_batch_finish): status words, capacity retries, pool growth and the per-graph counters, but no
+        record comes to the host.  The batch then feeds DeviceTranscriptSet.add_batch, device_transcript_stream and features_all as a
+        downloaded one does; result(), transcript_stream() and TranscriptSink.add_batch still need download()."""
+        _check(self._lib.ald_batch_finish(self._h))
+
+    def status_arrays(self):
+        """(status[n], num_paths[n], num_iterations[n]) int32 -- after finish() or download() (ald_batch_export_status)"""
+        st, npth, nit = (np.zeros(max(self.n, 1), np.int32) for _ in range(3))
+        _check(self._lib.ald_batch_export_status(self._h, *[C.c_void_p(a.ctypes.data) for a in (st, npth, nit)]))
+        return st[:self.n], npth[:self.n], nit[:self.n]
+
+    def last_finish_ms(self):
+        """stages of the last finish() in host milliseconds + bytes moved to the host (diagnostic)"""
+        v = [C.c_double(), C.c_double()]; nb = C.c_int64()
+        _check(self._lib.ald_batch_last_finish_ms(self._h, C.byref(v[0]), C.byref(v[1]), C.byref(nb)))
+        return dict(wait_kernel=v[0].value, status_retries=v[1].value, bytes_to_host=nb.value)
 
     def kernel_ms(self) -> float:
         return float(self._lib.ald_batch_last_kernel_ms(self._h))
@@ -649,7 +669,8 @@ class DeviceTranscriptSet:
         self.close()
 
     def add_batch(self, batch: "DecompBatch", sid=None, tid_base: int = 0, skip_single_exon: bool = False):
-        """Every transcript of a downloaded batch, graph by graph (== TranscriptSink.add_batch); the batch may be reused on return."""
+        """Every transcript of a downloaded or finished batch, graph by graph (== TranscriptSink.add_batch); the batch may be reused on
+        return.  From a finished batch (DecompBatch.finish) only the weights and the single-exon records come to the host."""
         sp = None
         if sid is not None:
             sid = np.ascontiguousarray(sid, np.int32); assert len(sid) == batch.n; sp = C.c_void_p(sid.ctypes.data)

@@ -192,6 +192,22 @@ int  ald_batch_upload(ald_batch *b);      /* H2D: the batch's arrays to ONE devi
 int  ald_batch_run(ald_batch *b);         /* launch decomposition kernels on the batch stream */
 int  ald_batch_sync(ald_batch *b);        /* wait for the stream                              */
 int  ald_batch_download(ald_batch *b);    /* D2H of status, path records (vertices + joined exons) and the kernel-written index; decode */
+/* End a run ON THE DEVICE: the first half of ald_batch_download and nothing of the second.  Waits for the stream, reads the status words,
+ * requeues ALD_ST_CAPACITY graphs one class up pass by pass, grows the record pool and runs again on ALD_ST_POOL_FULL (up to 8 times), then
+ * reads the per-graph counters: 20 bytes per graph + 16 come to the host, no record and no index entry does, nothing is decoded.  The batch
+ * is then FINISHED: status, path and iteration counts are known (ald_batch_export_status) and the consumers that read the records in HBM --
+ * ald_tset_dev_add_batch, ald_batch_device_transcript_stream, ald_batch_features_all[_ex] -- accept it as they accept a downloaded one, with
+ * the same results.  Everything that reads the host path table (get_result / get_path / export* / get_transcript, ald_tset_add_batch,
+ * ald_batch_transcript_stream, ald_batch_reduce_transcripts, raw_records, result_index, ald_batch_features) still needs ald_batch_download,
+ * which after a finish skips the status / retry stage, launches nothing and leaves ald_batch_last_kernel_ms as it is.  Idempotent;
+ * ALD_ERR_STATE before ald_batch_run; a trace buffer (ald_batch_enable_trace) is fetched by the download only. */
+int  ald_batch_finish(ald_batch *b);
+/* per graph: status, number of paths (0 unless the graph ended ALD_ST_OK / ALD_ST_SKIPPED_LARGE), main-loop iterations; any pointer may be
+ * NULL.  After ald_batch_finish or ald_batch_download (ALD_ERR_STATE otherwise). */
+int  ald_batch_export_status(const ald_batch *b, int32_t *status, int32_t *num_paths, int32_t *num_iterations);
+/* host milliseconds of the stages of the last ald_batch_finish (waiting for the kernels; status words, retries and counters) and the bytes
+ * it moved to the host */
+int  ald_batch_last_finish_ms(const ald_batch *b, double *wait_kernel_ms, double *status_retries_ms, int64_t *bytes_to_host);
 /* device milliseconds of the last ald_batch_run (hipEvents on the batch stream); <0 if n/a */
 double ald_batch_last_kernel_ms(const ald_batch *b);
 /* host milliseconds of the stages of the last ald_batch_download (diagnostic; nothing in the reference corresponds): waiting for the
@@ -265,7 +281,9 @@ int  ald_batch_features(const ald_batch *b, int32_t graph, const ald_graph_extra
  * (ald_batch_add_graph_raw) take the host routine inside the same call, on up to 16 threads, since their grouped graph exists only inside
  * the decomposition kernel.  Extras are ald_graph_extras for the whole batch: per-vertex arrays [sum of V], graphs back to back in
  * ticket order (vertex v of graph g at the sum of the vertex counts of graphs 0..g-1, plus v); per-graph values [graphs].  Any pointer may
- * be NULL (= zeros), and so may `x`.  ALD_ERR_STATE before ald_batch_download. */
+ * be NULL (= zeros), and so may `x`.  ALD_ERR_STATE before ald_batch_download / ald_batch_finish.  A batch that is only finished has no
+ * host records for the host routine: if it holds raw graphs, ald_batch_features_all_ex with ALD_FEAT_RAW_ON_DEVICE is the call
+ * (ALD_ERR_STATE without the flag). */
 typedef struct ald_batch_extras {
     const double  *boundary_loss1, *boundary_loss2, *boundary_loss3, *boundary_merged_loss;
     const int32_t *unbridge_leaving_count; const double *unbridge_leaving_ratio;
@@ -330,7 +348,7 @@ int  ald_batch_transcript_stream(const ald_batch *b, const int32_t *sid, int32_t
 /* The same stream, word for word, built by kernels and left in DEVICE memory (exon join, lengths, prefix sum, fill): for the RCCL
  * exchange of a multi-process host (ald_comm_gather_streams takes host or device pointers alike; torch.distributed a zero-copy view),
  * so that the finished transcripts travel HBM -> xGMI -> HBM of rank 0 without a detour through this rank's host memory.
- * Valid until the next run / reduction / stream call on this batch. */
+ * Valid until the next run / reduction / stream call on this batch.  Takes a downloaded or a finished (ald_batch_finish) batch. */
 int  ald_batch_device_transcript_stream(const ald_batch *b, const int32_t *sid, int32_t skip_single_exon, void **dev_words, int64_t *n_words);
 /* Merge such a stream, graph by graph in stream order (assembler.cc:1105-1133): coverage = log(1 + weight) is taken here, on the host;
  * tid = tid_base + ((graph + graph_offset) << 20 | path index), i.e. what ald_tset_add_batch gives the same graph in an unsharded batch */
@@ -369,8 +387,11 @@ int  ald_tset_flat_free(ald_tset_flat *f);
  * overlap rule is not transitive) stay in a host part inside the set, fed graph by graph in call order, and are spliced in by hash on
  * export.  The set owns its stream and scratch; one set is not thread-safe, two sets on two threads are.  Without a HIP device
  * ald_tset_dev_create returns ALD_ERR_NO_DEVICE.
- *   add_batch    == ald_tset_add_batch on a host set fed the same sequence.  Needs a DOWNLOADED batch (ALD_ERR_STATE otherwise) on the
- *                   set's device (ALD_ERR_INVALID otherwise); returns when the batch is no longer read: it may be cleared and reused.
+ *   add_batch    == ald_tset_add_batch on a host set fed the same sequence.  Needs a DOWNLOADED or FINISHED batch (ALD_ERR_STATE
+ *                   otherwise) on the set's device (ALD_ERR_INVALID otherwise); returns when the batch is no longer read: it may be
+ *                   cleared and reused.  From a finished batch (ald_batch_finish) no record pool comes to the host: 8 bytes per path (the
+ *                   weights, for coverage = log(1 + weight) with the host's libm) and, unless skip_single_exon, the records of the
+ *                   transcripts with fewer than two exons, compacted on the device; the items are bit for bit the same.
  *   add_stream   == ald_tset_add_stream (stream format of ald_batch_transcript_stream; words in host or device memory).  coverage[i] /
  *                   tid[i] (optional, one per transcript of the stream): as ald_tset_reduce_stream; NULL: log(1 + weight) and
  *                   tid_base + ((graph + graph_offset) << 20 | path index).  Unlike ald_tset_add_stream it takes skip_single_exon.
