@@ -319,6 +319,7 @@ int ald_batch_destroy(ald_batch *b)
     for(int c = 0; c < ALD_NUM_SLOTS; c++) b->d_slabs[c].release();
     for(DevBuf &d : b->red) d.release();
     for(DevBuf &d : b->dts) d.release();
+    for(DevBuf &d : b->tp) d.release();
     for(PinBuf &d : b->red_pin) d.release();
     b->feat.release();
     for(int q = 0; q < ALD_SIDE_STREAMS_MAX; q++) if(b->cstream[q]) { hipStreamSynchronize(b->cstream[q]); hipStreamDestroy(b->cstream[q]); }

@@ -91,6 +91,7 @@ struct ald_batch {
     rvec<uint32_t> tstream;                                // last transcript stream built from this batch (ald_batch_transcript_stream)
     DevBuf red[20]; PinBuf red_pin[8];                     // scratch of ald_batch_reduce_transcripts, kept across calls (tset_reduce.hip)
     DevBuf dts[3];                                         // ald_batch_device_transcript_stream: lengths / offsets / the stream itself
+    DevBuf tp[10]; std::vector<int64_t> tp_offsets;        // ald_batch_device_transcript_streams_by_owner (tset_partition.hip): scratch, the sub-streams, their offsets
     FeatTable feat;                                        // ald_batch_features_all
 };
 

@@ -10,10 +10,15 @@
 //
 // Exchange = sizes by ncclAllGather (one int64 per rank), payloads by grouped ncclSend / ncclRecv to rank 0 -- point-to-point, which
 // is what xGMI is; payload per rank is ~0.2 GB at 125 k graphs, i.e. ~1.4 ms per link.
-#include "ald_internal.h"
+//
+// The funnel has a second form that leaves no rank with more than its share: ald_comm_exchange_streams sends sub-stream r of every rank
+// (tset_partition.hip: the transcripts of the buckets rank r owns, hash % W == r) to rank r, all to all, where it folds into that rank's
+// resident set; ald_comm_gather_sets then brings the W disjoint sets to rank 0, which interleaves them by hash.
+#include "tset_front.h"          // ald_tset_flat (ald_comm_gather_sets), HCHK
 #include <rccl/rccl.h>
 #include <dlfcn.h>
 #include <mutex>
+#include <memory>
 
 namespace {
 
@@ -45,7 +50,6 @@ Rccl &rccl()
     return R;
 }
 #define NCHK(x) do { ncclResult_t r_ = (x); if(r_ != ncclSuccess) return ald_set_err(ALD_ERR_HIP, std::string(#x) + ": " + rccl().GetErrorString(r_)); } while(0)
-#define HCHK(x) do { hipError_t e_ = (x); if(e_ != hipSuccess) return ald_set_err(ALD_ERR_HIP, std::string(#x) + ": " + hipGetErrorString(e_)); } while(0)
 
 } // namespace
 
@@ -55,6 +59,8 @@ struct ald_comm {
     // two sets of receive buffers (rank 0): while the host merges what gather k brought, gather k + 1 receives and copies into the other set
     struct Set { DevBuf d_recv; PinBuf h_recv; std::vector<int64_t> offsets; std::vector<int32_t> goffs; std::vector<hipEvent_t> landed; hipEvent_t received = nullptr; bool open = false; } set[2];
     int cur = 1;                                   // the set of the gather begun last
+    // the exchange by bucket owner (ald_comm_exchange_streams) and the collection of the owners' sets (ald_comm_gather_sets): blocking, one buffer each
+    DevBuf d_xrecv; std::vector<int64_t> x_seg; std::vector<int32_t> x_goffs;
 };
 
 extern "C" {
@@ -93,7 +99,7 @@ int ald_comm_destroy(ald_comm *c)
     if(c->stream) { hipStreamSynchronize(c->stream); hipStreamDestroy(c->stream); }
     if(c->copy_stream) { hipStreamSynchronize(c->copy_stream); hipStreamDestroy(c->copy_stream); }
     if(c->comm) rccl().CommDestroy(c->comm);
-    c->d_send.release(); c->d_sizes.release();
+    c->d_send.release(); c->d_sizes.release(); c->d_xrecv.release();
     for(auto &st : c->set) { st.d_recv.release(); st.h_recv.release(); for(hipEvent_t e : st.landed) hipEventDestroy(e); if(st.received) hipEventDestroy(st.received); }
     delete c;
     return ALD_OK;
@@ -196,6 +202,179 @@ int ald_comm_gather_streams(ald_comm *c, const uint32_t *words, int64_t n_words,
     const int rc = ald_comm_gather_begin(c, words, n_words, graph_offset);
     if(rc != ALD_OK) return rc;
     return ald_comm_gather_wait(c, -1, all_words, offsets, graph_offsets);
+}
+
+/* sizes of all ranks by one AllGather of `per` int64 each: mine[per] -> all[world * per] on the host */
+static int exchange_sizes(ald_comm *c, const int64_t *mine, int per, std::vector<int64_t> &all)
+{
+    Rccl &R = rccl(); const int W = c->world; const size_t row = 8 * (size_t)per;
+    if(c->d_sizes.ensure(row * (size_t)(W + 1))) return ald_set_err(ALD_ERR_NOMEM, "size exchange buffer");
+    HCHK(hipMemcpyAsync(c->d_sizes.p, mine, row, hipMemcpyHostToDevice, c->stream));
+    NCHK(R.AllGather(c->d_sizes.p, (char*)c->d_sizes.p + row, (size_t)per, ncclInt64, c->comm, c->stream));
+    all.assign((size_t)W * (size_t)per, 0);
+    HCHK(hipMemcpyAsync(all.data(), (char*)c->d_sizes.p + row, row * (size_t)W, hipMemcpyDeviceToHost, c->stream));
+    HCHK(hipStreamSynchronize(c->stream));
+    return ALD_OK;
+}
+
+/* one group of Send / Recv, closed whatever happens: n_send sends (src[i], words[i] 8- or 4-byte elements, to[i]) and n_recv receives.  A
+ * failed Send / Recv is remembered, the group is closed (the calling thread must not stay in group mode) and the stream drained before
+ * the error goes back -- the gather's error handling. */
+struct Xfer { void *p; size_t count; int peer; };
+static int grouped(ald_comm *c, ncclDataType_t type, const std::vector<Xfer> &sends, const std::vector<Xfer> &recvs)
+{
+    Rccl &R = rccl();
+    NCHK(R.GroupStart());
+    ncclResult_t bad = ncclSuccess; const char *what = "";
+    for(size_t i = 0; i < sends.size() && bad == ncclSuccess; i++) { const ncclResult_t r_ = R.Send(sends[i].p, sends[i].count, type, sends[i].peer, c->comm, c->stream); if(r_ != ncclSuccess) { bad = r_; what = "ncclSend"; } }
+    for(size_t i = 0; i < recvs.size() && bad == ncclSuccess; i++) { const ncclResult_t r_ = R.Recv(recvs[i].p, recvs[i].count, type, recvs[i].peer, c->comm, c->stream); if(r_ != ncclSuccess) { bad = r_; what = "ncclRecv"; } }
+    const ncclResult_t ge = R.GroupEnd();
+    const hipError_t he = hipStreamSynchronize(c->stream);
+    if(bad != ncclSuccess || ge != ncclSuccess) return ald_set_err(ALD_ERR_HIP, std::string(bad != ncclSuccess ? what : "ncclGroupEnd") + ": " + R.GetErrorString(bad != ncclSuccess ? bad : ge));
+    if(he != hipSuccess) return ald_set_err(ALD_ERR_HIP, std::string("exchange stream: ") + hipGetErrorString(he));
+    return ALD_OK;
+}
+
+static bool in_device_memory(const void *p)
+{
+    hipPointerAttribute_t at; const bool dev = p && hipPointerGetAttributes(&at, p) == hipSuccess && at.type == hipMemoryTypeDevice;
+    (void)hipGetLastError();                                   // (a plain host pointer makes the query fail: not an error here)
+    return dev;
+}
+
+int ald_comm_exchange_streams(ald_comm *c, const uint32_t *words, const int64_t *offsets, int32_t graph_offset,
+                              const uint32_t **dev_words, const int64_t **seg_offsets, const int32_t **graph_offsets)
+{
+    if(!c || !offsets || !dev_words) return ALD_ERR_INVALID;
+    const int W = c->world;
+    for(int r = 0; r < W; r++) if(offsets[r] < 0 || offsets[r + 1] < offsets[r]) return ald_set_err(ALD_ERR_INVALID, "ald_comm_exchange_streams: offsets must ascend");
+    if(offsets[W] > offsets[0] && !words) return ALD_ERR_INVALID;
+    HCHK(hipSetDevice(c->device));
+    // sizes: every rank's W counts + its graph offset
+    std::vector<int64_t> mine((size_t)W + 1), all;
+    for(int r = 0; r < W; r++) mine[(size_t)r] = offsets[r + 1] - offsets[r];
+    mine[(size_t)W] = (int64_t)graph_offset;
+    { int rc = exchange_sizes(c, mine.data(), W + 1, all); if(rc != ALD_OK) return rc; }
+    auto count = [&](int from, int to) { return all[(size_t)from * (size_t)(W + 1) + (size_t)to]; };
+    c->x_seg.assign((size_t)W + 1, 0); c->x_goffs.assign((size_t)W, 0);
+    for(int q = 0; q < W; q++) { c->x_seg[(size_t)q + 1] = c->x_seg[(size_t)q] + count(q, c->rank); c->x_goffs[(size_t)q] = (int32_t)all[(size_t)q * (size_t)(W + 1) + (size_t)W]; }
+    // sub-streams that already live in HBM are sent from where they are; host memory is staged first
+    const uint32_t *src = words; const int64_t n_mine = offsets[W] - offsets[0];
+    if(n_mine > 0 && !in_device_memory(words)) {
+        if(c->d_send.ensure(4 * (size_t)n_mine + 64)) return ald_set_err(ALD_ERR_NOMEM, "send buffer");
+        HCHK(hipMemcpyAsync(c->d_send.p, words + offsets[0], 4 * (size_t)n_mine, hipMemcpyHostToDevice, c->stream));
+        src = (const uint32_t*)c->d_send.p - offsets[0];
+    }
+    if(c->d_xrecv.ensure(4 * (size_t)c->x_seg[(size_t)W] + 64)) return ald_set_err(ALD_ERR_NOMEM, "receive buffer");
+    std::vector<Xfer> sends, recvs;
+    for(int q = 0; q < W; q++) {
+        if(mine[(size_t)q]) sends.push_back(Xfer{(void*)(src + offsets[q]), (size_t)mine[(size_t)q], q});
+        if(count(q, c->rank)) recvs.push_back(Xfer{(uint32_t*)c->d_xrecv.p + c->x_seg[(size_t)q], (size_t)count(q, c->rank), q});
+    }
+    { int rc = grouped(c, ncclUint32, sends, recvs); if(rc != ALD_OK) return rc; }
+    *dev_words = (const uint32_t*)c->d_xrecv.p;
+    if(seg_offsets) *seg_offsets = c->x_seg.data();
+    if(graph_offsets) *graph_offsets = c->x_goffs.data();
+    return ALD_OK;
+}
+
+} // extern "C"
+
+/* a flat set as ONE run of 8-byte words: n, exons, samples, then every array, each padded to a multiple of 8 bytes */
+namespace {
+template<class V> void put(std::vector<uint64_t> &buf, const V &v, size_t n)
+{
+    const size_t bytes = n * sizeof(v[0]), at = buf.size();
+    buf.resize(at + (bytes + 7) / 8, 0);
+    if(bytes) memcpy(buf.data() + at, v.data(), bytes);
+}
+template<class T> const T *take(const uint64_t *&p, size_t n) { const T *r = (const T*)p; p += (n * sizeof(T) + 7) / 8; return r; }
+struct FlatView {
+    int64_t n, ne, ns; const uint64_t *hash; const int32_t *count, *count1, *count2; const char *strand; const double *coverage, *cov2, *conf, *abd; const int64_t *tid, *exon_offset, *sample_offset;
+    const int32_t *exon_lr, *sample_sid, *sample_count1; const double *sample_cov2, *sample_conf, *sample_abd;
+};
+void pack(const ald_tset_flat &f, std::vector<uint64_t> &buf)
+{
+    const size_t n = f.hash.size(), ne = f.exon_lr.size() / 2, ns = f.sample_sid.size();
+    buf.assign({(uint64_t)n, (uint64_t)ne, (uint64_t)ns});
+    put(buf, f.hash, n); put(buf, f.count, n); put(buf, f.count1, n); put(buf, f.count2, n); put(buf, f.strand, n); put(buf, f.coverage, n); put(buf, f.cov2, n); put(buf, f.conf, n); put(buf, f.abd, n);
+    put(buf, f.tid, n); put(buf, f.exon_offset, n + 1); put(buf, f.sample_offset, n + 1); put(buf, f.exon_lr, 2 * ne); put(buf, f.sample_sid, ns); put(buf, f.sample_count1, ns);
+    put(buf, f.sample_cov2, ns); put(buf, f.sample_conf, ns); put(buf, f.sample_abd, ns);
+}
+bool unpack(const uint64_t *p, int64_t words, FlatView &v)
+{
+    if(words < 3) return false;
+    const uint64_t *end = p + words;
+    v.n = (int64_t)p[0]; v.ne = (int64_t)p[1]; v.ns = (int64_t)p[2]; p += 3;
+    if(v.n < 0 || v.ne < 0 || v.ns < 0 || v.n > words || v.ne > words || v.ns > words) return false;
+    const size_t n = (size_t)v.n, ne = (size_t)v.ne, ns = (size_t)v.ns;
+    v.hash = take<uint64_t>(p, n); v.count = take<int32_t>(p, n); v.count1 = take<int32_t>(p, n); v.count2 = take<int32_t>(p, n); v.strand = take<char>(p, n);
+    v.coverage = take<double>(p, n); v.cov2 = take<double>(p, n); v.conf = take<double>(p, n); v.abd = take<double>(p, n); v.tid = take<int64_t>(p, n);
+    v.exon_offset = take<int64_t>(p, n + 1); v.sample_offset = take<int64_t>(p, n + 1); v.exon_lr = take<int32_t>(p, 2 * ne); v.sample_sid = take<int32_t>(p, ns); v.sample_count1 = take<int32_t>(p, ns);
+    v.sample_cov2 = take<double>(p, ns); v.sample_conf = take<double>(p, ns); v.sample_abd = take<double>(p, ns);
+    return p == end && v.exon_offset[n] == v.ne && v.sample_offset[n] == v.ns;
+}
+} // namespace
+
+extern "C" {
+
+int ald_comm_gather_sets(ald_comm *c, const ald_tset_flat *f, ald_tset_flat **out)
+{
+    if(!c || !f || !out) return ALD_ERR_INVALID;
+    *out = nullptr;
+    const int W = c->world;
+    HCHK(hipSetDevice(c->device));
+    // a bucket must live wholly on its owner: a foreign one is announced in the size exchange, and every rank leaves before anybody waits
+    bool foreign = false;
+    for(size_t i = 0; i < f->hash.size() && !foreign; i++) foreign = (int)(f->hash[i] % (uint64_t)W) != c->rank;
+    std::vector<uint64_t> buf;
+    if(!foreign) pack(*f, buf);
+    int64_t mine = foreign ? -1 : (int64_t)buf.size();
+    std::vector<int64_t> all;
+    { int rc = exchange_sizes(c, &mine, 1, all); if(rc != ALD_OK) return rc; }
+    for(int r = 0; r < W; r++) if(all[(size_t)r] < 0) return ald_set_err(ALD_ERR_INVALID, "ald_comm_gather_sets: the set of rank " + std::to_string(r) + " holds a bucket it does not own");
+    std::vector<int64_t> at((size_t)W + 1, 0);
+    for(int r = 0; r < W; r++) at[(size_t)r + 1] = at[(size_t)r] + all[(size_t)r];
+    if(c->d_send.ensure(8 * buf.size() + 64) || (c->rank == 0 && c->d_xrecv.ensure(8 * (size_t)at[(size_t)W] + 64))) return ald_set_err(ALD_ERR_NOMEM, "set exchange buffers");
+    HCHK(hipMemcpyAsync(c->d_send.p, buf.data(), 8 * buf.size(), hipMemcpyHostToDevice, c->stream));
+    std::vector<Xfer> sends, recvs;
+    sends.push_back(Xfer{c->d_send.p, buf.size(), 0});
+    if(c->rank == 0) for(int r = 0; r < W; r++) recvs.push_back(Xfer{(uint64_t*)c->d_xrecv.p + at[(size_t)r], (size_t)all[(size_t)r], r});
+    { int rc = grouped(c, ncclUint64, sends, recvs); if(rc != ALD_OK) return rc; }
+    if(c->rank != 0) return ALD_OK;
+    std::vector<uint64_t> got((size_t)at[(size_t)W]);
+    HCHK(hipMemcpy(got.data(), c->d_xrecv.p, 8 * got.size(), hipMemcpyDeviceToHost));
+    std::vector<FlatView> v((size_t)W);
+    for(int r = 0; r < W; r++) if(!unpack(got.data() + at[(size_t)r], all[(size_t)r], v[(size_t)r])) return ald_set_err(ALD_ERR_INVALID, "ald_comm_gather_sets: the set of rank " + std::to_string(r) + " arrived damaged");
+    // W-way merge by hash: the ranks' hashes ascend and are disjoint, so the next bucket is the smallest head, taken whole
+    int64_t N = 0, NE = 0, NS = 0; for(auto &x : v) { N += x.n; NE += x.ne; NS += x.ns; }
+    std::vector<int32_t> from((size_t)N); std::vector<int64_t> idx((size_t)N);
+    { std::vector<int64_t> cur((size_t)W, 0);
+      for(int64_t k = 0; k < N; ) {
+          int best = -1;
+          for(int r = 0; r < W; r++) if(cur[(size_t)r] < v[(size_t)r].n && (best < 0 || v[(size_t)r].hash[cur[(size_t)r]] < v[(size_t)best].hash[cur[(size_t)best]])) best = r;
+          const FlatView &x = v[(size_t)best]; int64_t &i = cur[(size_t)best]; const uint64_t h = x.hash[i];
+          while(i < x.n && x.hash[i] == h) { from[(size_t)k] = best; idx[(size_t)k] = i; k++; i++; }
+      } }
+    std::unique_ptr<ald_tset_flat> Fp(new ald_tset_flat()); ald_tset_flat *F = Fp.get();
+    const size_t NT = (size_t)N;
+    F->hash.resize(NT); F->count.resize(NT); F->strand.resize(NT); F->coverage.resize(NT); F->cov2.resize(NT); F->conf.resize(NT); F->abd.resize(NT); F->count1.resize(NT); F->count2.resize(NT); F->tid.resize(NT);
+    F->exon_offset.assign(NT + 1, 0); F->sample_offset.assign(NT + 1, 0);
+    F->exon_lr.resize(2 * (size_t)NE); F->sample_sid.resize((size_t)NS); F->sample_count1.resize((size_t)NS); F->sample_cov2.resize((size_t)NS); F->sample_conf.resize((size_t)NS); F->sample_abd.resize((size_t)NS);
+    for(size_t k = 0; k < NT; k++) {
+        const FlatView &x = v[(size_t)from[k]]; const int64_t i = idx[k];
+        F->hash[k] = x.hash[i]; F->count[k] = x.count[i]; F->strand[k] = x.strand[i]; F->coverage[k] = x.coverage[i]; F->cov2[k] = x.cov2[i]; F->conf[k] = x.conf[i]; F->abd[k] = x.abd[i];
+        F->count1[k] = x.count1[i]; F->count2[k] = x.count2[i]; F->tid[k] = x.tid[i];
+        const int64_t e0 = x.exon_offset[i], e1 = x.exon_offset[i + 1], s0 = x.sample_offset[i], s1 = x.sample_offset[i + 1];
+        const int64_t eo = F->exon_offset[k], so = F->sample_offset[k];
+        if(e0 < 0 || e1 < e0 || e1 > x.ne || s0 < 0 || s1 < s0 || s1 > x.ns || eo + (e1 - e0) > NE || so + (s1 - s0) > NS) return ald_set_err(ALD_ERR_INVALID, "ald_comm_gather_sets: inconsistent offsets in a received set");
+        F->exon_offset[k + 1] = eo + (e1 - e0); F->sample_offset[k + 1] = so + (s1 - s0);
+        if(e1 > e0) memcpy(&F->exon_lr[2 * (size_t)eo], x.exon_lr + 2 * e0, 8 * (size_t)(e1 - e0));
+        for(int64_t s = s0; s < s1; s++) { const size_t d = (size_t)(so + (s - s0)); F->sample_sid[d] = x.sample_sid[s]; F->sample_count1[d] = x.sample_count1[s]; F->sample_cov2[d] = x.sample_cov2[s]; F->sample_conf[d] = x.sample_conf[s]; F->sample_abd[d] = x.sample_abd[s]; }
+        F->n_host_items++;
+    }
+    *out = Fp.release();
+    return ALD_OK;
 }
 
 } // extern "C"

@@ -18,6 +18,21 @@ inline unsigned grid_for(int64_t n) { return (unsigned)((n + TX_BLOCK - 1) / TX_
 struct TxIn { const unsigned long long *roff; const uint32_t *pool; int64_t np; };
 __host__ __device__ inline const int32_t *rec_exons(const uint32_t *r) { return (const int32_t*)(r + REC_HDR_WORDS + r[2]); }
 
+// transcript::get_intron_chain_hashing (transcript.cc:183-201, util.cc:38-46) over the flat exon words; 64-bit size_t arithmetic as on the host
+__host__ __device__ inline uint64_t chain_key_dev(const int32_t *x, int n_words)
+{
+    uint64_t h = (uint64_t)(n_words - 2);
+    for(int k = 1; k + 1 < n_words; k++) h ^= (uint64_t)(int64_t)x[k] + 0x9e3779b9ull + (h << 6) + (h >> 2);
+    return (h & 0x7FFFFFFFull) + 1;
+}
+// the bucket of ANY transcript, as transcript_sink::chain_key has it: no exon -> 0, one exon -> its mid-point bin in int32 arithmetic
+__host__ __device__ inline uint64_t bucket_key_dev(const int32_t *x, int n_words)
+{
+    if(n_words < 2) return 0;
+    if(n_words == 2) return (uint64_t)(int64_t)((x[0] + x[1]) / 10000) + 1;
+    return chain_key_dev(x, n_words);
+}
+
 // first: path (in (graph, path) order) whose record the item takes its exons, strand and id from
 struct TxGroup { int64_t first; unsigned long long first_off; int32_t count, count1, lo, hi; double coverage, cov2, conf, abd; uint32_t bucket; int32_t nw, graph, path, strand, pad; };
 // one (group, sample) run: the per-sample maxima of a group's members from one sample

@@ -40,14 +40,6 @@ __global__ void ix_order(const int32_t *n_paths, const int64_t *pbegin, const lo
 }
 __global__ void ix_widen(const int32_t *n_paths, int n, int64_t *len) { const int g = (int)((int64_t)blockIdx.x * TX_BLOCK + threadIdx.x); if(g <= n) len[g] = g < n ? (int64_t)n_paths[g] : 0; }
 
-// transcript::get_intron_chain_hashing (transcript.cc:183-201, util.cc:38-46) over the flat exon words; 64-bit size_t arithmetic as on the host
-__host__ __device__ inline uint64_t chain_key_dev(const int32_t *x, int n_words)
-{
-    uint64_t h = (uint64_t)(n_words - 2);
-    for(int k = 1; k + 1 < n_words; k++) h ^= (uint64_t)(int64_t)x[k] + 0x9e3779b9ull + (h << 6) + (h >> 2);
-    return (h & 0x7FFFFFFFull) + 1;
-}
-
 // WEIGHT: also weight[p] = the record's weight (word 6), dense in (graph, path) order -- consecutive lanes write consecutive doubles -- for a
 // caller that has no host copy of the records and takes coverage = log(1 + weight) on the host (tx_front_coverage)
 template<bool WEIGHT> __global__ void tx_build(TxIn in, int32_t *nwords, uint64_t *key, int32_t *graph_of, double *weight)

@@ -239,6 +239,9 @@ def load_library():
     lib.ald_batch_enable_trace.argtypes = [C.c_void_p, C.c_int32]
     lib.ald_batch_device_records.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_int64)]
     lib.ald_batch_device_transcript_stream.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_void_p), C.POINTER(C.c_int64)]
+    lib.ald_batch_device_transcript_streams_by_owner.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_void_p), C.POINTER(C.POINTER(C.c_int64))]
+    lib.ald_transcript_bucket.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_uint64)]
+    lib.ald_tset_split_stream.argtypes = [C.c_int32, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p]
     lib.ald_records_add_graph_offset.argtypes = [C.c_void_p, C.c_int64, C.c_int32]
     lib.ald_tset_destroy.argtypes = [C.c_void_p]
     lib.ald_tset_create.argtypes = [C.c_double, C.POINTER(C.c_void_p)]
@@ -455,6 +458,17 @@ class DecompBatch:
             sid = np.ascontiguousarray(sid, np.int32); assert len(sid) == self.n; sp = C.c_void_p(sid.ctypes.data)
         _check(self._lib.ald_batch_device_transcript_stream(self._h, sp, C.c_int32(int(skip_single_exon)), C.byref(p), C.byref(n)))
         return int(p.value or 0), int(n.value)
+
+    def device_transcript_streams_by_owner(self, world: int, sid=None, skip_single_exon: bool = False):
+        """(device pointer, offsets[world + 1] in words): the finished transcripts split by bucket owner on the device -- sub-stream r, at
+        words offsets[r] .. offsets[r + 1], holds the transcripts whose bucket hash % world == r, in (graph, path) order, in
+        transcript_stream()'s record format: what rank r folds after the all-to-all exchange (ald_comm_exchange_streams)."""
+        p = C.c_void_p(); o = C.POINTER(C.c_int64)()
+        sp = None
+        if sid is not None:
+            sid = np.ascontiguousarray(sid, np.int32); assert len(sid) == self.n; sp = C.c_void_p(sid.ctypes.data)
+        _check(self._lib.ald_batch_device_transcript_streams_by_owner(self._h, sp, C.c_int32(int(skip_single_exon)), C.c_int32(int(world)), C.byref(p), C.byref(o)))
+        return int(p.value or 0), np.ctypeslib.as_array(o, shape=(int(world) + 1,)).copy()
 
     def result(self) -> DecompResult:
         return export_via(self._lib.ald_batch_export, self._h, self.n, check=_check)
@@ -735,6 +749,31 @@ def reduce_stream(words: np.ndarray, coverage=None, tid=None, tid_base: int = 0,
     finally:
         lib.ald_tset_flat_free(h)
     return items, dict(device_ms=st[0].value, total_ms=st[1].value, device_groups=st[2].value, host_items=st[3].value)
+
+
+def transcript_bucket(exons) -> int:
+    """transcript::get_intron_chain_hashing of exons = [(l, r), ...]: the bucket of the transcript in a transcript_set; its owner in a
+    world of W ranks is transcript_bucket(exons) % W."""
+    lr = np.ascontiguousarray(np.array(exons, np.int32).reshape(-1))
+    h = C.c_uint64()
+    _check(load_library().ald_transcript_bucket(C.c_void_p(lr.ctypes.data) if lr.size else None, C.c_int32(lr.size // 2), C.byref(h)))
+    return int(h.value)
+
+
+def split_stream(words, world: int, device: int = 0):
+    """A transcript stream split by bucket owner on the GPU (ald_tset_split_stream) -> (words, offsets[world + 1]): the W sub-streams back
+    to back, each in the order of the input; numpy in, numpy out (split_stream_into takes raw host or device pointers)."""
+    words = np.ascontiguousarray(words, np.uint32)
+    out = np.zeros(max(words.size, 1), np.uint32); offs = np.zeros(max(int(world), 0) + 1, np.int64)
+    split_stream_into(words.ctypes.data, words.size, world, out.ctypes.data, offs, device)
+    return out[:words.size], offs
+
+
+def split_stream_into(src_ptr: int, n_words: int, world: int, dst_ptr: int, offsets: np.ndarray, device: int = 0):
+    """ald_tset_split_stream on raw pointers: source and destination may each be host or device memory; offsets: int64 [world + 1]"""
+    assert offsets.dtype == np.int64 and offsets.flags.c_contiguous and offsets.size >= max(int(world), 0) + 1
+    _check(load_library().ald_tset_split_stream(C.c_int32(device), C.c_void_p(src_ptr), C.c_int64(n_words), C.c_int32(int(world)), C.c_void_p(dst_ptr), C.c_void_p(offsets.ctypes.data)))
+    return offsets
 
 
 def _two_pass(fn, *args) -> str:

@@ -350,6 +350,21 @@ int  ald_batch_transcript_stream(const ald_batch *b, const int32_t *sid, int32_t
  * so that the finished transcripts travel HBM -> xGMI -> HBM of rank 0 without a detour through this rank's host memory.
  * Valid until the next run / reduction / stream call on this batch.  Takes a downloaded or a finished (ald_batch_finish) batch. */
 int  ald_batch_device_transcript_stream(const ald_batch *b, const int32_t *sid, int32_t skip_single_exon, void **dev_words, int64_t *n_words);
+/* ---- the same transcripts split by BUCKET OWNER for a world of W ranks ----
+ * transcript_set::add only ever touches one bucket at a time (transcript_set.cc:83-120, 149-175), so the rank that owns bucket h, h % W,
+ * computes it bit for bit as an unsharded run would once it gets the bucket's transcripts in ascending global (graph, path) order.
+ * transcript::get_intron_chain_hashing (transcript.cc:183-201); owner of the bucket in a world of W ranks = hash % W */
+int  ald_transcript_bucket(const int32_t *exon_lr, int32_t n_exons, uint64_t *hash);
+/* downloaded or finished batch -> W sub-streams back to back in device memory, built by kernels straight from the path records: sub-stream
+ * r = the transcripts with hash % world == r, in their (graph, path) order, in the record format above.  offsets: host array [world + 1],
+ * in words; valid as ald_batch_device_transcript_stream's result is.  world in 1..64 (ALD_ERR_INVALID otherwise); world == 1 gives
+ * ald_batch_device_transcript_stream's words. */
+int  ald_batch_device_transcript_streams_by_owner(const ald_batch *b, const int32_t *sid, int32_t skip_single_exon, int32_t world,
+                                                  void **dev_words, const int64_t **offsets);
+/* the same split for a stream that already exists (host or device memory); out_words: caller's buffer of n_words words, host or
+ * device; offsets: caller's [world + 1].  The record walk that finds the transcript boundaries runs on the host; owner, placement and
+ * copy run in the kernels.  A malformed or non-ascending stream: ALD_ERR_INVALID, as in ald_tset_add_stream. */
+int  ald_tset_split_stream(int32_t device, const uint32_t *words, int64_t n_words, int32_t world, uint32_t *out_words, int64_t *offsets);
 /* Merge such a stream, graph by graph in stream order (assembler.cc:1105-1133): coverage = log(1 + weight) is taken here, on the host;
  * tid = tid_base + ((graph + graph_offset) << 20 | path index), i.e. what ald_tset_add_batch gives the same graph in an unsharded batch */
 int  ald_tset_add_stream(ald_tset *t, const uint32_t *words, int64_t n_words, int32_t graph_offset, int64_t tid_base);
@@ -432,6 +447,20 @@ int  ald_comm_gather_streams(ald_comm *c, const uint32_t *words, int64_t n_words
  * before it has merged gather k: what a _wait handed out stays valid until the SECOND next _begin on this communicator. */
 int  ald_comm_gather_begin(ald_comm *c, const uint32_t *words, int64_t n_words, int32_t graph_offset);
 int  ald_comm_gather_wait(ald_comm *c, int32_t upto, const uint32_t **all_words /* rank 0 */, const int64_t **offsets /* [world + 1] */, const int32_t **graph_offsets /* [world] */);
+/* ---- the exchange by bucket owner: no rank folds more than its own buckets ----
+ * collective: rank q passes its W sub-streams (ald_batch_device_transcript_streams_by_owner / ald_tset_split_stream: device or host pointer
+ * + offsets[world + 1]) and the global id of its first graph; on return rank r holds, in DEVICE memory, the segments addressed to it back to
+ * back in source-rank order (== ascending global graph id): (*dev_words + seg_offsets[q], seg_offsets[q + 1] - seg_offsets[q]) with
+ * graph_offsets[q].  Valid until the next exchange on this communicator.  The owner folds them in rank order:
+ * ald_tset_dev_add_stream(set, dev_words + seg_offsets[q], len_q, NULL, NULL, graph_offsets[q], tid_base, 0) for q = 0 .. W - 1.
+ * Blocking; sizes by one ncclAllGather, payloads by one group of ncclSend / ncclRecv (pairs of length zero are skipped on both sides). */
+int  ald_comm_exchange_streams(ald_comm *c, const uint32_t *words, const int64_t *offsets, int32_t graph_offset,
+                               const uint32_t **dev_words, const int64_t **seg_offsets /* [world + 1] */, const int32_t **graph_offsets /* [world] */);
+/* collective: every rank passes a snapshot of its set (ald_tset_dev_snapshot, or a flat of its own); rank 0 receives ONE flat with all
+ * items in the reference's iteration order (ascending hash; a bucket lives wholly on one rank, so its inner order is kept) and frees it
+ * with ald_tset_flat_free; *all stays NULL on the other ranks.  A set that holds an item with hash % world != rank makes EVERY rank
+ * return ALD_ERR_INVALID (it is announced in the size exchange; nobody waits). */
+int  ald_comm_gather_sets(ald_comm *c, const ald_tset_flat *mine, ald_tset_flat **all);
 int  ald_comm_destroy(ald_comm *c);
 /* transcript_set::add(transcript_set&) (transcript_set.cc:156-175): every bucket of src zipped into dst; src is left empty */
 int  ald_tset_merge(ald_tset *dst, ald_tset *src);

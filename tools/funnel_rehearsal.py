@@ -8,7 +8,13 @@ and merges it (ald_tset_add_stream) while stream r + 1 is still being copied.  P
 landed, the merge per stream, the whole step, and the same with the next step's gather begun BEFORE the merge (the buffers exist twice).
 What the rehearsal cannot show is the xGMI time of the real receive: 8 x ~180 MB over 7 links of ~50 GB/s is a few milliseconds.
 
-    ALD_RCCL_LIB=tests/_build/libmock_rccl.so python tools/funnel_rehearsal.py [W=8] [graphs per rank=125000] [steps=3]
+    ALD_RCCL_LIB=tests/_build/libmock_rccl.so python tools/funnel_rehearsal.py [W=8] [graphs per rank=125000] [steps=3] [mode=funnel]
+
+mode `owners`: the exchange by bucket owner instead of the funnel.  Per step every rank splits its stream by owner on the device
+(ald_tset_split_stream, device to device), exchanges the sub-streams all to all (ald_comm_exchange_streams) and folds the W segments it
+received, in rank order, into its OWN resident set (ald_tset_dev_add_stream); after the last step the sets go to rank 0
+(ald_comm_gather_sets).  Printed per rank: the transcripts folded per step, the fold time, the share of all transcripts and of all items it
+holds.  W ranks share one GPU and this host's cores here, so the fold times are upper bounds; what the run shows is the share.
 """
 import ctypes as C, os, subprocess, sys, threading, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -16,6 +22,8 @@ sys.path.insert(0, ROOT)
 W = int(sys.argv[1]) if len(sys.argv) > 1 else 8
 NG = int(sys.argv[2]) if len(sys.argv) > 2 else 125000
 STEPS = int(sys.argv[3]) if len(sys.argv) > 3 else 3
+MODE = sys.argv[4] if len(sys.argv) > 4 else "funnel"
+assert MODE in ("funnel", "owners"), MODE
 mock = os.environ.get("ALD_RCCL_LIB")
 if not mock:
     mock = os.path.join(ROOT, "tests", "_build", "libmock_rccl.so"); os.makedirs(os.path.dirname(mock), exist_ok=True)
@@ -44,6 +52,76 @@ torch.cuda.synchronize()
 print(f"{W} shards of {NG} graphs decomposed in {time.perf_counter() - t0:.1f} s; stream sizes (MB): {[round(4 * s.numel() / 1e6, 1) for s in streams]}", flush=True)
 
 uid = (C.c_uint8 * 128)(); assert lib.ald_comm_unique_id(uid) == 0, lib.ald_last_error()
+
+
+def owners():
+    lib.ald_comm_exchange_streams.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_void_p), C.POINTER(C.POINTER(C.c_int64)), C.POINTER(C.POINTER(C.c_int32))]
+    lib.ald_comm_gather_sets.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]
+    bar = threading.Barrier(W); rep = [None] * W; err = []; total = {}
+
+    def n_transcripts(words):                                    # the records of a stream, counted on the host
+        w = words.cpu().numpy().view(np.uint32); n = 0; o = 0
+        while o < w.size:
+            o += 12 + 2 * int(w[o + 5]); n += 1
+        return n
+
+    def rank(r):
+        try:
+            comm = C.c_void_p(); assert lib.ald_comm_create(uid, W, r, 0, C.byref(comm)) == 0, lib.ald_last_error()
+            src = streams[r]; split = torch.empty_like(src); offs = np.zeros(W + 1, np.int64); torch.cuda.synchronize()
+            steps = []
+            with A.DeviceTranscriptSet(0, 0.8) as ds:
+                for k in range(STEPS):
+                    bar.wait(); t0 = time.perf_counter()
+                    A.split_stream_into(src.data_ptr(), src.numel(), W, split.data_ptr(), offs)
+                    t1 = time.perf_counter()
+                    words = C.c_void_p(); seg = C.POINTER(C.c_int64)(); goffs = C.POINTER(C.c_int32)()
+                    assert lib.ald_comm_exchange_streams(comm, C.c_void_p(split.data_ptr()), C.c_void_p(offs.ctypes.data), C.c_int32(r * NG), C.byref(words), C.byref(seg), C.byref(goffs)) == 0, lib.ald_last_error()
+                    t2 = time.perf_counter(); got = seg[W]
+                    if k == 0:
+                        total[r] = n_transcripts(_device_words(words.value, got, dev)) if got else 0; bar.wait(); t2 = time.perf_counter()
+                    for q in range(W):
+                        n = seg[q + 1] - seg[q]
+                        if n:
+                            assert lib.ald_tset_dev_add_stream(ds._h, C.c_void_p(words.value + 4 * seg[q]), C.c_int64(n), None, None, C.c_int32(goffs[q]), C.c_int64((k + 1) << 44), C.c_int32(0)) == 0, lib.ald_last_error()
+                    t3 = time.perf_counter()
+                    steps.append((t1 - t0, t2 - t1, t3 - t2, 4 * got / 1e6))
+                bar.wait(); t0 = time.perf_counter()
+                snap = C.c_void_p(); assert lib.ald_tset_dev_snapshot(ds._h, C.byref(snap)) == 0, lib.ald_last_error()
+                items = C.c_int64(); assert lib.ald_tset_flat_size(snap, C.byref(items), None, None) == 0
+                allf = C.c_void_p(); assert lib.ald_comm_gather_sets(comm, snap, C.byref(allf)) == 0, lib.ald_last_error()
+                t1 = time.perf_counter(); merged = C.c_int64(0)
+                if allf.value:
+                    assert lib.ald_tset_flat_size(allf, C.byref(merged), None, None) == 0; lib.ald_tset_flat_free(allf)
+                lib.ald_tset_flat_free(snap)
+                rep[r] = (steps, items.value, merged.value, t1 - t0)
+            bar.wait()
+            assert lib.ald_comm_destroy(comm) == 0
+        except BaseException as e:
+            err.append(e)
+            try: bar.abort()
+            except Exception: pass
+
+    ths = [threading.Thread(target=rank, args=(r,)) for r in range(W)]
+    for t in ths: t.start()
+    for t in ths: t.join()
+    if err: raise err[0]
+    all_tx = sum(total.values()); all_items = sum(x[1] for x in rep)
+    for r in range(W):
+        steps, items, merged, tg = rep[r]
+        print(f"rank {r}: folds {total[r]} of {all_tx} transcripts per step (share {total[r] / all_tx:.4f}), {steps[0][3]:.0f} MB received | " +
+              " | ".join(f"step {k}: split {1e3 * a:6.1f} ms, exchange {1e3 * b:6.1f} ms, fold {1e3 * c:7.1f} ms" for k, (a, b, c, _) in enumerate(steps)) +
+              f" | holds {items} of {all_items} items (share {items / all_items:.4f})", flush=True)
+    worst = max(max(c for _, _, c, _ in rep[r][0][1:] or rep[r][0]) for r in range(W))
+    print(f"largest share of the transcripts folded by one rank: {max(total.values()) / all_tx:.4f} (1 / W = {1 / W:.4f}); largest share of the items held: {max(x[1] for x in rep) / all_items:.4f}")
+    print(f"slowest fold of one rank after the first step: {1e3 * worst:.1f} ms for {W * NG} bundles of the step = {W * NG / worst / 1e6:.2f} M bundles/s with all {W} ranks on ONE GPU and one host")
+    print(f"sets to rank 0 (snapshot + ald_comm_gather_sets, {rep[0][2]} items in the merged flat): {1e3 * rep[0][3]:.1f} ms, once per run")
+    assert rep[0][2] == all_items
+    print("OWNERS_OK")
+
+
+if MODE == "owners":
+    owners(); sys.exit(0)
 sink = A.TranscriptSink(0.8)
 bar = threading.Barrier(W); rep = {}; err = []
 
