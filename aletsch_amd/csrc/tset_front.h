@@ -39,7 +39,16 @@ struct TxGroup { int64_t first; unsigned long long first_off; int32_t count, cou
 struct TxSample { int32_t gid, sid, count1, pad; double cov2, conf, abd; };
 
 // scratch of a front end run (owned by a batch or a resident set and kept across calls, or temporary for the stream entry point)
-struct RedScratch { DevBuf *red; PinBuf *pin; hipStream_t st; };
+// d2h (optional): every byte the front end copies device -> host is added to it (ald_tset_dev_stream_stats)
+struct RedScratch { DevBuf *red; PinBuf *pin; hipStream_t st; int64_t *d2h = nullptr; };
+inline void tx_count_d2h(const RedScratch &S, size_t bytes) { if(S.d2h) *S.d2h += (int64_t)bytes; }
+// is p device memory?  (a plain host pointer makes the query fail: not an error here)
+inline bool tx_on_device(const void *p)
+{
+    hipPointerAttribute_t at; const bool dev = p && hipPointerGetAttributes(&at, p) == hipSuccess && at.type == hipMemoryTypeDevice;
+    (void)hipGetLastError();
+    return dev;
+}
 
 // What the front end leaves behind.  In S.red: [2] coverage per path, [3] weight per path (tx_front_sort without h_cov), [6] sorted group keys, [7] sorted (group, sample) keys,
 // [8] path of every sorted position (sidx), [11] head flags, [12] 1-based group id of every sorted position, [13] TxGroup[n_groups],
@@ -47,8 +56,10 @@ struct RedScratch { DevBuf *red; PinBuf *pin; hipStream_t st; };
 // ev0 (optional): recorded once the inputs are on the device, i.e. where the device time of the caller's section begins.
 // ev_w / h_cov: only when the coverages are made from the records (tx_front_sort without h_cov): the event behind the D2H of the weights,
 // and the coverages tx_front_coverage computed (pinned, S.pin[5]).
+// d_cov (set by the caller, optional): coverage per path already in DEVICE memory (a device stream folded with the caller's coverages):
+// tx_front_sort without h_cov then copies it device to device and neither fetches the weights nor needs tx_front_coverage.
 struct TxFront { int64_t np = 0, n_dev = 0; int32_t n_groups = 0, n_runs = 0; std::vector<int64_t> host_paths; hipEvent_t ev0 = nullptr; bool sid_on_device = false;
-                 hipEvent_t ev_w = nullptr; const double *h_cov = nullptr; };
+                 hipEvent_t ev_w = nullptr; const double *h_cov = nullptr; const double *d_cov = nullptr; };
 inline const uint64_t *tx_skey(const RedScratch &S) { return (const uint64_t*)S.red[6].p; }
 inline const int64_t *tx_sidx(const RedScratch &S) { return (const int64_t*)S.red[8].p; }
 inline const int32_t *tx_head(const RedScratch &S) { return (const int32_t*)S.red[11].p; }
@@ -80,8 +91,18 @@ int tx_front_fold(RedScratch S, TxIn in, TxFront &F, const int64_t *start_idx, c
 void tx_host_singles(aletsch::transcript_sink &into, const std::vector<int64_t> &host_paths, const uint32_t *h_pool, const unsigned long long *h_roff,
                      const double *h_cov, const int64_t *h_tid, const int32_t *sid, const int64_t *label, int64_t tid_base, const unsigned long long *h_off = nullptr);
 // a transcript stream (format of ald_batch_transcript_stream) turned into records the front end reads
-struct StreamRecords { std::vector<uint32_t> pool; std::vector<unsigned long long> roff; std::vector<double> cov; std::vector<int32_t> sid; std::vector<int64_t> label, tids; };
+struct StreamRecords { std::vector<uint32_t> pool; std::vector<unsigned long long> roff; std::vector<double> cov; std::vector<int32_t> sid; std::vector<int64_t> label, tids; int64_t n_transcripts = 0; };
 int tx_stream_records(const uint32_t *words, int64_t n_words, const double *coverage, const int64_t *tid, int32_t skip_single_exon, int64_t graph_offset, StreamRecords &R);
+// The same walk on the device (tset_index.hip): the transcript boundaries of a stream in DEVICE memory by pointer doubling over the record
+// lengths.  toff[i] = first word of transcript i, toff[nt] = n_words; gid[i] = 1-based run of equal graph ids transcript i belongs to
+// (runs counted before any single-exon filter, as tx_stream_records pushes label / sid before it skips); label[k] = graph id of run k +
+// graph_offset, sid[k] = word 2 of its first transcript.  All four live in ix[] (the caller's, IX_BUFS DevBufs) until the next call.
+// Kernels on `st`; ONE copy of 40 bytes (counts + flags, into `pin`) and one synchronisation.  e0 / e1 (optional): recorded around the
+// kernels, ms = the time between them.  Malformed or descending: ALD_ERR_INVALID as tx_stream_records; n_words == 0 launches nothing;
+// n_words >= 2^31: ALD_ERR_INVALID (the callers keep the host walk for such a stream).
+enum { IX_BUFS = 10 };
+struct StreamIndex { const unsigned long long *toff = nullptr; const int32_t *gid = nullptr; const int64_t *label = nullptr; const int32_t *sid = nullptr; int64_t nt = 0, ng = 0; double ms = 0; };
+int tx_stream_index(hipStream_t st, DevBuf *ix, PinBuf &pin, hipEvent_t e0, hipEvent_t e1, const uint32_t *d_words, int64_t n_words, int64_t graph_offset, StreamIndex &I);
 // the path table of a downloaded or finished batch in (graph, path) order on the device (b->d_ordoff), built once per run
 int device_path_table(ald_batch *b);
 

@@ -13,7 +13,7 @@
 //   tp_bounds   1 lane / sorted place    where the owner changes: offsets[owner]
 //   tp_emit     16 lanes / transcript    header + exon words, consecutive lanes on consecutive words (as ts_emit)
 // Both sources go through the same kernels: REC = the path records of a batch (exon join and header layout of ts_emit, no unsplit stream
-// is built first), !REC = the transcripts of a stream at the word offsets the host's record walk found.
+// is built first), !REC = the transcripts of a stream at the word offsets the stream index found (tset_index.hip: kernels, not a host walk).
 #include "tset_front.h"
 #include <hipcub/hipcub.hpp>
 
@@ -102,13 +102,6 @@ template<bool REC> int tp_fill(hipStream_t st, DevBuf *tp, TpSrc s, const int32_
     return ALD_OK;
 }
 
-bool on_device(const void *p)
-{
-    hipPointerAttribute_t at; const bool dev = p && hipPointerGetAttributes(&at, p) == hipSuccess && at.type == hipMemoryTypeDevice;
-    (void)hipGetLastError();                                // (a plain host pointer makes the query fail: not an error here)
-    return dev;
-}
-
 } // namespace
 
 extern "C" {
@@ -154,30 +147,40 @@ int ald_tset_split_stream(int32_t device, const uint32_t *words, int64_t n_words
     HCHK(hipSetDevice(device));
     for(int r = 0; r <= world; r++) offsets[r] = 0;
     if(n_words == 0) return ALD_OK;
-    const bool src_dev = on_device(words), dst_dev = on_device(out_words);
-    // the record walk that finds the transcript boundaries runs on the host (as tx_stream_records walks): a device stream comes over for it
-    std::vector<uint32_t> staged;
-    const uint32_t *h_words = words;
-    if(src_dev) { staged.resize((size_t)n_words); HCHK(hipMemcpy(staged.data(), words, 4 * (size_t)n_words, hipMemcpyDeviceToHost)); h_words = staged.data(); }
-    std::vector<unsigned long long> toff;
-    { int64_t last = -1;
-      for(int64_t o = 0; o < n_words; ) {
-          if(o + ALD_TS_HDR > n_words) return ald_set_err(ALD_ERR_INVALID, "malformed transcript stream");
-          const int64_t len = ALD_TS_HDR + 2 * (int64_t)h_words[o + 5];
-          if((int32_t)h_words[o + 5] < 0 || o + len > n_words) return ald_set_err(ALD_ERR_INVALID, "malformed transcript stream");
-          const int64_t g = (int64_t)h_words[o];
-          if(g < last) return ald_set_err(ALD_ERR_INVALID, "transcript stream not in ascending graph order");
-          last = g; toff.push_back((unsigned long long)o); o += len;
-      } }
-    const int64_t nt = (int64_t)toff.size();
-    DevBuf tp[TP_BUFS], d_in, d_off, d_out;
-    struct Rel { DevBuf *t, *a, *b, *c; ~Rel() { for(int i = 0; i < TP_BUFS; i++) t[i].release(); a->release(); b->release(); c->release(); } } rel{tp, &d_in, &d_off, &d_out};
+    const bool src_dev = tx_on_device(words), dst_dev = tx_on_device(out_words);
+    DevBuf tp[TP_BUFS], ix[IX_BUFS], d_in, d_off, d_out; PinBuf pin;
+    struct Rel { DevBuf *t, *x, *a, *b, *c; PinBuf *p; ~Rel() { for(int i = 0; i < TP_BUFS; i++) t[i].release(); for(int i = 0; i < IX_BUFS; i++) x[i].release(); a->release(); b->release(); c->release(); p->release(); } } rel{tp, ix, &d_in, &d_off, &d_out, &pin};
     hipStream_t st = nullptr; HCHK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
     struct StRel { hipStream_t s; ~StRel() { hipStreamDestroy(s); } } strel{st};
-    if(d_off.ensure(8 * (size_t)nt) || (!src_dev && d_in.ensure(4 * (size_t)n_words)) || (!dst_dev && d_out.ensure(4 * (size_t)n_words))) return ald_set_err(ALD_ERR_NOMEM, "owner split buffers");
-    if(!src_dev) HCHK(hipMemcpyAsync(d_in.p, words, 4 * (size_t)n_words, hipMemcpyHostToDevice, st));
-    HCHK(hipMemcpyAsync(d_off.p, toff.data(), 8 * (size_t)nt, hipMemcpyHostToDevice, st));
-    TpSrc s; s.base = src_dev ? words : (const uint32_t*)d_in.p; s.off = (const unsigned long long*)d_off.p; s.n = nt;
+    if((!src_dev && d_in.ensure(4 * (size_t)n_words)) || (!dst_dev && d_out.ensure(4 * (size_t)n_words))) return ald_set_err(ALD_ERR_NOMEM, "owner split buffers");
+    TpSrc s; s.base = src_dev ? words : (const uint32_t*)d_in.p;
+    if(n_words < (int64_t)1 << 31) {
+        // the transcript boundaries come from the stream index: a device stream stays where it is, a host stream is uploaded once
+        if(!src_dev) HCHK(hipMemcpyAsync(d_in.p, words, 4 * (size_t)n_words, hipMemcpyHostToDevice, st));
+        StreamIndex I;
+        { int rc = tx_stream_index(st, ix, pin, nullptr, nullptr, s.base, n_words, 0, I); if(rc != ALD_OK) return rc; }
+        s.off = I.toff; s.n = I.nt;
+    } else {
+        // 2^31 words or more, beyond the index's 32-bit nodes: the record walk on the host (as tx_stream_records walks); a device stream comes over for it
+        std::vector<uint32_t> staged;
+        const uint32_t *h_words = words;
+        if(src_dev) { staged.resize((size_t)n_words); HCHK(hipMemcpy(staged.data(), words, 4 * (size_t)n_words, hipMemcpyDeviceToHost)); h_words = staged.data(); }
+        std::vector<unsigned long long> toff;
+        { int64_t last = -1;
+          for(int64_t o = 0; o < n_words; ) {
+              if(o + ALD_TS_HDR > n_words) return ald_set_err(ALD_ERR_INVALID, "malformed transcript stream");
+              const int64_t len = ALD_TS_HDR + 2 * (int64_t)h_words[o + 5];
+              if((int32_t)h_words[o + 5] < 0 || o + len > n_words) return ald_set_err(ALD_ERR_INVALID, "malformed transcript stream");
+              const int64_t g = (int64_t)h_words[o];
+              if(g < last) return ald_set_err(ALD_ERR_INVALID, "transcript stream not in ascending graph order");
+              last = g; toff.push_back((unsigned long long)o); o += len;
+          } }
+        const int64_t nt = (int64_t)toff.size();
+        if(d_off.ensure(8 * (size_t)nt)) return ald_set_err(ALD_ERR_NOMEM, "owner split buffers");
+        if(!src_dev) HCHK(hipMemcpyAsync(d_in.p, words, 4 * (size_t)n_words, hipMemcpyHostToDevice, st));
+        HCHK(hipMemcpy(d_off.p, toff.data(), 8 * (size_t)nt, hipMemcpyHostToDevice));
+        s.off = (const unsigned long long*)d_off.p; s.n = nt;
+    }
     std::vector<int64_t> h_offs((size_t)world + 1, 0);
     { int rc = tp_place<false>(st, tp, s, 0, world, h_offs.data()); if(rc != ALD_OK) return rc; }
     if(h_offs[(size_t)world] != n_words) return ald_set_err(ALD_ERR_HIP, "owner split: the sub-streams do not add up to the stream");

@@ -223,19 +223,20 @@ int tx_front_sort(RedScratch S, TxIn in, const double *h_cov, int n_graphs, cons
     DevBuf &d_cov = S.red[2], &d_w = S.red[3], &d_nw = S.red[4], &d_key = S.red[5], &d_key2 = S.red[6], &d_idx = S.red[7], &d_idx2 = S.red[8], &d_graph = S.red[9],
            &d_sid = S.red[10], &d_head = S.red[11], &d_gid = S.red[12], &d_tmp = S.red[14], &d_head2 = S.red[15], &d_rid = S.red[16], &d_pos = S.red[18], &d_pos2 = S.red[19];
     PinBuf &p_key = S.pin[0], &p_w = S.pin[4], &p_cov = S.pin[5];
-    const bool from_records = h_cov == nullptr;
+    const bool from_records = h_cov == nullptr && F.d_cov == nullptr;
     if(from_records && !F.ev_w) return ald_set_err(ALD_ERR_INVALID, "tx_front_sort: coverage from the records needs an event");
     if(p_key.ensure(8 * (size_t)np, true) || (from_records && (p_w.ensure(8 * (size_t)np, true) || p_cov.ensure(8 * (size_t)np)))) return ald_set_err(ALD_ERR_NOMEM, "pinned reduction buffers");
     if(d_cov.ensure(8 * (size_t)np) || d_nw.ensure(4 * (size_t)np) || d_key.ensure(8 * (size_t)np) || (from_records && d_w.ensure(8 * (size_t)np))
        || d_key2.ensure(8 * (size_t)np) || d_idx.ensure(8 * (size_t)np) || d_idx2.ensure(8 * (size_t)np) || d_graph.ensure(4 * (size_t)np) || d_head.ensure(4 * (size_t)np) || d_gid.ensure(4 * (size_t)np)
        || d_head2.ensure(4 * (size_t)np) || d_rid.ensure(4 * (size_t)np) || d_pos.ensure(8 * (size_t)np) || d_pos2.ensure(8 * (size_t)np) || (sid && d_sid.ensure(4 * (size_t)n_graphs + 4))) return ald_set_err(ALD_ERR_NOMEM, "reduction buffers");
     hipStream_t st = S.st;
-    if(!from_records) HCHK(hipMemcpyAsync(d_cov.p, h_cov, 8 * (size_t)np, hipMemcpyHostToDevice, st));
+    if(h_cov) HCHK(hipMemcpyAsync(d_cov.p, h_cov, 8 * (size_t)np, hipMemcpyHostToDevice, st));
+    else if(F.d_cov) HCHK(hipMemcpyAsync(d_cov.p, F.d_cov, 8 * (size_t)np, hipMemcpyDeviceToDevice, st));
     if(sid) HCHK(hipMemcpyAsync(d_sid.p, sid, 4 * (size_t)n_graphs, hipMemcpyHostToDevice, st));
     if(F.ev0) HCHK(hipEventRecord(F.ev0, st));
     if(from_records) {
         hipLaunchKernelGGL(tx_build<true>, dim3(grid_for(np)), dim3(TX_BLOCK), 0, st, in, (int32_t*)d_nw.p, (uint64_t*)d_key.p, (int32_t*)d_graph.p, (double*)d_w.p);
-        HCHK(hipMemcpyAsync(p_w.p, d_w.p, 8 * (size_t)np, hipMemcpyDeviceToHost, st));
+        HCHK(hipMemcpyAsync(p_w.p, d_w.p, 8 * (size_t)np, hipMemcpyDeviceToHost, st)); tx_count_d2h(S, 8 * (size_t)np);
         HCHK(hipEventRecord(F.ev_w, st));
     } else hipLaunchKernelGGL(tx_build<false>, dim3(grid_for(np)), dim3(TX_BLOCK), 0, st, in, (int32_t*)d_nw.p, (uint64_t*)d_key.p, (int32_t*)d_graph.p, (double*)nullptr);
     hipLaunchKernelGGL(tx_iota, dim3(grid_for(np)), dim3(TX_BLOCK), 0, st, (int64_t*)d_idx.p, np);
@@ -247,7 +248,7 @@ int tx_front_sort(RedScratch S, TxIn in, const double *h_cov, int n_graphs, cons
     if(d_tmp.ensure(std::max(tmp_bytes, scan_bytes) + 256)) return ald_set_err(ALD_ERR_NOMEM, "sort scratch");
     HCHK(hipcub::DeviceRadixSort::SortPairs(d_tmp.p, tmp_bytes, (const uint64_t*)d_key.p, (uint64_t*)d_key2.p, (const int64_t*)d_idx.p, (int64_t*)d_idx2.p, (int)np, 0, 64, st));
     // how many went to the device: the sorted keys below TX_HOST (tx_front_heads looks)
-    HCHK(hipMemcpyAsync(p_key.p, d_key2.p, 8 * (size_t)np, hipMemcpyDeviceToHost, st));
+    HCHK(hipMemcpyAsync(p_key.p, d_key2.p, 8 * (size_t)np, hipMemcpyDeviceToHost, st)); tx_count_d2h(S, 8 * (size_t)np);
     return ALD_OK;
 }
 
@@ -279,11 +280,11 @@ int tx_front_heads(RedScratch S, TxIn in, TxFront &F)
         HCHK(hipcub::DeviceScan::InclusiveSum(nullptr, scan_bytes, (const int32_t*)d_head.p, (int32_t*)d_gid.p, (int)np, st));      // (d_tmp holds at least this: tx_front_sort)
         hipLaunchKernelGGL(tx_heads, dim3(grid_for(n_dev)), dim3(TX_BLOCK), 0, st, in, (const uint64_t*)d_key2.p, (const int64_t*)d_idx2.p, n_dev, (int32_t*)d_head.p);
         HCHK(hipcub::DeviceScan::InclusiveSum(d_tmp.p, scan_bytes, (const int32_t*)d_head.p, (int32_t*)d_gid.p, (int)n_dev, st));
-        HCHK(hipMemcpyAsync(&F.n_groups, (int32_t*)d_gid.p + (n_dev - 1), 4, hipMemcpyDeviceToHost, st));
+        HCHK(hipMemcpyAsync(&F.n_groups, (int32_t*)d_gid.p + (n_dev - 1), 4, hipMemcpyDeviceToHost, st)); tx_count_d2h(S, 4);
     }
     // the transcripts left to the host: the tail of the sorted order (key TX_HOST; the stable sort kept them in (graph, path) order)
     F.host_paths.resize((size_t)(np - n_dev));
-    if(np > n_dev) HCHK(hipMemcpyAsync(F.host_paths.data(), (const int64_t*)d_idx2.p + n_dev, 8 * (size_t)(np - n_dev), hipMemcpyDeviceToHost, st));
+    if(np > n_dev) { HCHK(hipMemcpyAsync(F.host_paths.data(), (const int64_t*)d_idx2.p + n_dev, 8 * (size_t)(np - n_dev), hipMemcpyDeviceToHost, st)); tx_count_d2h(S, 8 * (size_t)(np - n_dev)); }
     HCHK(hipStreamSynchronize(st));
     if(hipGetLastError() != hipSuccess) return ald_set_err(ALD_ERR_HIP, "a reduction kernel failed to launch");
     return ALD_OK;
@@ -311,13 +312,13 @@ int tx_compact_singles(RedScratch S, TxIn in, const TxFront &F, DevBuf &d_out, c
     HCHK(hipcub::DeviceScan::ExclusiveSum(nullptr, scan_bytes, (const int64_t*)d_len.p, (int64_t*)d_at.p, (int)(ns + 1), st));
     if(d_tmp.ensure(scan_bytes + 256)) return ald_set_err(ALD_ERR_NOMEM, "scan scratch");
     HCHK(hipcub::DeviceScan::ExclusiveSum(d_tmp.p, scan_bytes, (const int64_t*)d_len.p, (int64_t*)d_at.p, (int)(ns + 1), st));
-    HCHK(hipMemcpyAsync(p_off.p, d_at.p, 8 * (size_t)(ns + 1), hipMemcpyDeviceToHost, st));
+    HCHK(hipMemcpyAsync(p_off.p, d_at.p, 8 * (size_t)(ns + 1), hipMemcpyDeviceToHost, st)); tx_count_d2h(S, 8 * (size_t)(ns + 1));
     HCHK(hipStreamSynchronize(st));
     const int64_t total = ((const int64_t*)p_off.p)[ns];
     if(total < 0 || d_out.ensure(4 * (size_t)total + 64) || p_words.ensure(4 * (size_t)total + 64, true)) return ald_set_err(ALD_ERR_NOMEM, "single-exon records");
     hipLaunchKernelGGL(sx_copy, dim3(grid_for(16 * ns)), dim3(TX_BLOCK), 0, st, in, hp, (const int64_t*)d_at.p, ns, (uint32_t*)d_out.p);
     if(hipGetLastError() != hipSuccess) return ald_set_err(ALD_ERR_HIP, "a compaction kernel failed to launch");
-    if(total) HCHK(hipMemcpyAsync(p_words.p, d_out.p, 4 * (size_t)total, hipMemcpyDeviceToHost, st));
+    if(total) { HCHK(hipMemcpyAsync(p_words.p, d_out.p, 4 * (size_t)total, hipMemcpyDeviceToHost, st)); tx_count_d2h(S, 4 * (size_t)total); }
     *h_words = (const uint32_t*)p_words.p; *h_off = (const unsigned long long*)p_off.p;
     return ALD_OK;
 }
@@ -342,7 +343,7 @@ int tx_front_fold(RedScratch S, TxIn in, TxFront &F, const int64_t *start_idx, c
     HCHK(hipcub::DeviceRadixSort::SortPairs(d_tmp.p, tmp_bytes, (const uint64_t*)d_key.p, (uint64_t*)d_idx.p /* sorted key2 */, (const int64_t*)d_pos.p, (int64_t*)d_pos2.p, (int)n_dev, 0, 64, st));
     hipLaunchKernelGGL(tx_sheads, dim3(grid_for(n_dev)), dim3(TX_BLOCK), 0, st, (const uint64_t*)d_idx.p, n_dev, (int32_t*)d_head2.p);
     HCHK(hipcub::DeviceScan::InclusiveSum(d_tmp.p, scan_bytes, (const int32_t*)d_head2.p, (int32_t*)d_rid.p, (int)n_dev, st));
-    HCHK(hipMemcpyAsync(&F.n_runs, (int32_t*)d_rid.p + (n_dev - 1), 4, hipMemcpyDeviceToHost, st));
+    HCHK(hipMemcpyAsync(&F.n_runs, (int32_t*)d_rid.p + (n_dev - 1), 4, hipMemcpyDeviceToHost, st)); tx_count_d2h(S, 4);
     HCHK(hipStreamSynchronize(st));
     if(d_samples.ensure(sizeof(TxSample) * (size_t)F.n_runs)) return ald_set_err(ALD_ERR_NOMEM, "sample records");
     hipLaunchKernelGGL(tx_sfold, dim3(grid_for(n_dev)), dim3(TX_BLOCK), 0, st, in, (const uint64_t*)d_idx.p, (const int64_t*)d_pos2.p, sidx, (const int32_t*)d_head2.p, (const int32_t*)d_rid.p, n_dev,
@@ -402,6 +403,7 @@ int tx_stream_records(const uint32_t *words, int64_t n_words, const double *cove
         double w; memcpy(&w, words + o + 6, 8); cov.push_back(coverage ? coverage[ti] : log(1.0 + w)); if(tid) tids.push_back(tid[ti]);
         o += len;
     }
+    R.n_transcripts = ti + 1;
     return ALD_OK;
 }
 

@@ -23,6 +23,12 @@
 // A batch that ald_batch_finish ended has no host copy of its records: the front end then runs in its halves (tset_front.h: tx_front_sort /
 // _coverage / _heads) -- the key pass also writes the weights, the host takes log(1 + w) under the sort -- and the single-exon records
 // the host part merges are compacted on the device (tx_compact_singles).
+// A stream in DEVICE memory (a segment the owner exchange left there) takes the same form: its transcript boundaries come from the stream
+// index (tset_index.hip), then
+//   sr_len / scans         which transcripts stay (skip_single_exon), where their scratch records begin, their ordinal among the kept
+//   sr_emit                16 lanes / transcript: the scratch record tx_stream_records would build, word for word, straight into d_pool;
+//                          the caller's coverage / tid (uploaded, indexed by stream ordinal) gathered to the kept ordinal
+// so no word of the stream reaches host memory: per call the counts, label / sid per group, and what a finished batch brings.
 #include "tset_front.h"
 #include <hipcub/hipcub.hpp>
 #include <algorithm>
@@ -117,6 +123,38 @@ struct InSet {                       // a second resident set (ald_tset_dev_merg
 };
 
 __device__ inline int64_t lane_id() { return (int64_t)blockIdx.x * TX_BLOCK + threadIdx.x; }
+
+// ---- a device stream as scratch records (tx_stream_records on the device).  keep[i]: transcript i stays; len[i]: words of its record
+__global__ void sr_len(const uint32_t *words, const unsigned long long *toff, int64_t nt, int skip_single, int64_t *len, int32_t *keep)
+{
+    const int64_t i = lane_id();
+    if(i > nt) return;
+    if(i == nt) { len[i] = 0; keep[i] = 0; return; }        // (the exclusive scans over nt + 1 entries leave the totals in the last one)
+    const int64_t k = 2 * (int64_t)words[toff[i] + 5];
+    const bool kp = !(skip_single && k <= 2);
+    len[i] = kp ? (int64_t)rec_words(2, (unsigned)k) : 0; keep[i] = kp ? 1 : 0;
+}
+// header + two placeholder vertices + the exon words (18 + k words: even, so no padding word), consecutive lanes on consecutive words
+__global__ void sr_emit(const uint32_t *words, const unsigned long long *toff, const int32_t *gid, const int64_t *at, const int32_t *kord, int64_t nt,
+                        const double *cov_in, const int64_t *tid_in, uint32_t *pool, unsigned long long *roff, double *cov, int64_t *tid)
+{
+    const int64_t i = lane_id() / 16; const int l = (int)(threadIdx.x & 15);
+    if(i >= nt) return;
+    const int64_t o = at[i];
+    if(at[i + 1] == o) return;
+    const uint32_t *w = words + toff[i]; uint32_t *r = pool + o;
+    const int k = 2 * (int)w[5];
+    uint32_t v;
+    switch(l) { case 0: v = (uint32_t)(gid[i] - 1); break; case 1: v = w[1]; break; case 2: v = 2; break; case 4: v = w[4]; break; case 5: v = w[3] & 0xFF; break;
+                case 6: v = w[6]; break; case 7: v = w[7]; break;          /* weight */
+                case 8: v = w[10]; break; case 9: v = w[11]; break;        /* abd    */
+                case 10: v = w[8]; break; case 11: v = w[9]; break;        /* conf   */
+                case REC_NEXW: v = (uint32_t)k; break; default: v = 0; break; }
+    r[l] = v;
+    if(l < 2) r[REC_HDR_WORDS + l] = 0;
+    for(int q = l; q < k; q += 16) r[REC_HDR_WORDS + 2 + q] = w[ALD_TS_HDR + q];
+    if(l == 0) { const int32_t p = kord[i]; roff[p] = (unsigned long long)o; if(cov_in) cov[p] = cov_in[i]; if(tid_in) tid[p] = tid_in[i]; }
+}
 
 // head position (in the sorted member order) of every group
 __global__ void rs_ghead(const int32_t *head, const int32_t *gid, int64_t n_dev, int32_t *ghead)
@@ -271,13 +309,19 @@ struct ald_tset_dev {
     aletsch::transcript_sink single;                        // transcripts with fewer than two exons, in call order
     DevBuf red[20], d_pool, d_roff, d_label, d_tid; PinBuf pin[8];          // front end scratch (the set's own, never a batch's)
     DevBuf w[16];                                           // merge-path scratch ([14]: the compacted single-exon records of a finished batch)
+    DevBuf ix[IX_BUFS], sr[9]; PinBuf pin_ix, pin_sr;       // a device stream: the stream index, the record build (sr_len / sr_emit)
+    hipEvent_t ev_i0 = nullptr, ev_i1 = nullptr;            // around the index kernels
     double last_device_ms = 0, last_call_ms = 0;
+    // of the last ald_tset_dev_add_stream (ald_tset_dev_stream_stats)
+    int64_t st_transcripts = 0, st_groups = 0, st_words_to_host = 0, bytes_to_host = 0; double st_index_ms = 0;
     explicit ald_tset_dev(double ov) : single(ov) {}
     SetBufs &res() { return buf[cur]; }
     const SetBufs &res() const { return buf[cur]; }
     ~ald_tset_dev() {
         for(auto &b : buf) b.release();
         for(auto &d : red) d.release(); for(auto &d : w) d.release(); for(auto &p : pin) p.release();
+        for(auto &d : ix) d.release(); for(auto &d : sr) d.release(); pin_ix.release(); pin_sr.release();
+        if(ev_i0) hipEventDestroy(ev_i0); if(ev_i1) hipEventDestroy(ev_i1);
         d_pool.release(); d_roff.release(); d_label.release(); d_tid.release();
         if(ev0) hipEventDestroy(ev0); if(ev1) hipEventDestroy(ev1); if(ev_w) hipEventDestroy(ev_w);
         if(st) hipStreamDestroy(st);
@@ -308,6 +352,7 @@ template<class In> int merge_path(ald_tset_dev *s, In B, const int64_t *match, c
     if(p_cnt.ensure(64)) return ald_set_err(ALD_ERR_NOMEM, "pinned counter");
     int64_t *hc = (int64_t*)p_cnt.p;
     { int32_t *u = (int32_t*)(hc + 4); HCHK(hipMemcpyAsync(u, (const int32_t*)d_ub.p + nB, 4, hipMemcpyDeviceToHost, st)); HCHK(hipStreamSynchronize(st)); hc[0] = *u; }
+    s->bytes_to_host += 4 + 16;                             // (this count and the two totals below)
     const int64_t N = nA + hc[0];
     if(d_slot.ensure(8 * (size_t)(N + 1)) || d_ecnt.ensure(8 * (size_t)(N + 1)) || d_scnt.ensure(8 * (size_t)(N + 1)) || Ob.ensure_items(N)) return ald_set_err(ALD_ERR_NOMEM, "resident set items");
     if(N > 0) hipLaunchKernelGGL(rs_slots, dim3(grid_for(nA + nB)), dim3(TX_BLOCK), 0, st, nA, nB, (const int32_t*)d_shift.p, match, ins, (const int32_t*)d_ub.p, (int64_t*)d_slot.p);
@@ -337,37 +382,41 @@ template<class In> int merge_path(ald_tset_dev *s, In B, const int64_t *match, c
 // h_pool = null (a batch that ald_batch_finish ended: its records never left HBM): the two things the host part needs are fetched here --
 // the weights, 8 bytes per path, for coverage = log(1 + weight) with the host's libm, under the sort; and, unless skip_single_exon, the
 // records of the transcripts with fewer than two exons, compacted on the device.
+// d_cov / d_tid (a device stream folded with the caller's coverage[] / tid[], h_pool = null): the same per path in DEVICE memory -- the
+// weights then stay where they are; h_cov / h_tid are only read for the transcripts the host part merges.
 int add_records(ald_tset_dev *s, const uint32_t *d_pool, const unsigned long long *d_roff, const uint32_t *h_pool, const unsigned long long *h_roff, const double *h_cov,
-                const int64_t *h_tid, int64_t np, int n_graphs, const int32_t *sid, const int64_t *label, int64_t tid_base, int32_t skip_single_exon)
+                const int64_t *h_tid, int64_t np, int n_graphs, const int32_t *sid, const int64_t *label, int64_t tid_base, int32_t skip_single_exon,
+                const double *d_cov = nullptr, const int64_t *d_tid = nullptr)
 {
     s->last_device_ms = 0;
     if(np == 0) return ALD_OK;
     hipStream_t st = s->st;
-    RedScratch S; S.red = s->red; S.pin = s->pin; S.st = st;
+    RedScratch S; S.red = s->red; S.pin = s->pin; S.st = st; S.d2h = &s->bytes_to_host;
     TxIn in; in.roff = d_roff; in.pool = d_pool; in.np = np;
     TxFront X; X.ev0 = s->ev0;
     const unsigned long long *h_off = nullptr;             // != null: h_pool holds the single-exon records only, in the order of X.host_paths
     if(h_pool) { int rc = tx_front_groups(S, in, h_cov, n_graphs, sid, X); if(rc != ALD_OK) return rc; }
     else {
-        X.ev_w = s->ev_w;
+        X.ev_w = s->ev_w; X.d_cov = d_cov;
         { int rc = tx_front_sort(S, in, nullptr, n_graphs, sid, X); if(rc != ALD_OK) return rc; }
-        { int rc = tx_front_coverage(S, X); if(rc != ALD_OK) return rc; }
+        if(!d_cov) { int rc = tx_front_coverage(S, X); if(rc != ALD_OK) return rc; }
         { int rc = tx_front_heads(S, in, X); if(rc != ALD_OK) return rc; }
-        h_cov = X.h_cov; h_roff = nullptr;
+        if(!d_cov) h_cov = X.h_cov;
+        h_roff = nullptr;
         if(!skip_single_exon) { int rc = tx_compact_singles(S, in, X, s->w[14], &h_pool, &h_off); if(rc != ALD_OK) return rc; }      // read behind the stream waits below
     }
     if(X.n_groups > 0) {
         const int64_t G = X.n_groups;
         DevBuf &d_ghead = s->w[0], &d_perm = s->w[1], &d_match = s->w[2], &d_ins = s->w[3], &d_unm = s->w[4], &d_start = s->w[5], &d_sbeg = s->w[13], &d_lab = s->d_label, &d_ptid = s->d_tid;
         if(d_ghead.ensure(4 * (size_t)G) || d_perm.ensure(4 * (size_t)G) || d_match.ensure(8 * (size_t)G) || d_ins.ensure(8 * (size_t)G) || d_unm.ensure(4 * (size_t)(G + 1))
-           || d_start.ensure(8 * (size_t)G) || d_sbeg.ensure(8 * (size_t)(G + 1)) || (label && d_lab.ensure(8 * (size_t)n_graphs + 8)) || (h_tid && d_ptid.ensure(8 * (size_t)np + 8)))
+           || d_start.ensure(8 * (size_t)G) || d_sbeg.ensure(8 * (size_t)(G + 1)) || (label && d_lab.ensure(8 * (size_t)n_graphs + 8)) || (h_tid && !d_tid && d_ptid.ensure(8 * (size_t)np + 8)))
             return ald_set_err(ALD_ERR_NOMEM, "resident set batch scratch");
         if(label) HCHK(hipMemcpyAsync(d_lab.p, label, 8 * (size_t)n_graphs, hipMemcpyHostToDevice, st));
-        if(h_tid) HCHK(hipMemcpyAsync(d_ptid.p, h_tid, 8 * (size_t)np, hipMemcpyHostToDevice, st));
+        if(h_tid && !d_tid) HCHK(hipMemcpyAsync(d_ptid.p, h_tid, 8 * (size_t)np, hipMemcpyHostToDevice, st));
         hipLaunchKernelGGL(rs_ghead, dim3(grid_for(X.n_dev)), dim3(TX_BLOCK), 0, st, tx_head(S), tx_gid(S), X.n_dev, (int32_t*)d_ghead.p);
         hipLaunchKernelGGL(rs_order, dim3(grid_for(G)), dim3(TX_BLOCK), 0, st, in, tx_sidx(S), (const int32_t*)d_ghead.p, tx_skey(S), G, (int32_t*)d_perm.p);
         InBatch B; B.in = in; B.sidx = tx_sidx(S); B.ghead = (const int32_t*)d_ghead.p; B.skey = tx_skey(S); B.perm = (const int32_t*)d_perm.p;
-        B.grp = nullptr; B.smp = nullptr; B.sbeg = nullptr; B.tid_base = tid_base; B.label = label ? (const int64_t*)d_lab.p : nullptr; B.ptid = h_tid ? (const int64_t*)d_ptid.p : nullptr; B.n = G;
+        B.grp = nullptr; B.smp = nullptr; B.sbeg = nullptr; B.tid_base = tid_base; B.label = label ? (const int64_t*)d_lab.p : nullptr; B.ptid = d_tid ? d_tid : h_tid ? (const int64_t*)d_ptid.p : nullptr; B.n = G;
         const SetView A = s->res().view();
         hipLaunchKernelGGL(rs_match<InBatch>, dim3(grid_for(G + 1)), dim3(TX_BLOCK), 0, st, A, B, (int64_t*)d_match.p, (int64_t*)d_ins.p, (int32_t*)d_unm.p);
         hipLaunchKernelGGL(rs_start, dim3(grid_for(G)), dim3(TX_BLOCK), 0, st, (const int32_t*)d_perm.p, (const int64_t*)d_match.p, G, (int64_t*)d_start.p);
@@ -383,6 +432,48 @@ int add_records(ald_tset_dev *s, const uint32_t *d_pool, const unsigned long lon
     // the device part is in: the transcripts with fewer than two exons, graph by graph, into the host part
     if(!skip_single_exon) tx_host_singles(s->single, X.host_paths, h_pool, h_roff, h_cov, h_tid, sid, label, tid_base, h_off);
     return ALD_OK;
+}
+
+// A stream in device memory: index, record build, fold -- nothing proportional to n_words leaves HBM.  coverage / tid: the caller's (host
+// memory, one per transcript of the stream, left-out ones counted) or null.  A refused stream returns before anything of the set changes.
+int add_device_stream(ald_tset_dev *s, const uint32_t *d_words, int64_t n_words, const double *coverage, const int64_t *tid, int64_t graph_offset, int64_t tid_base, int32_t skip_single_exon)
+{
+    hipStream_t st = s->st;
+    StreamIndex I;
+    { const int rc = tx_stream_index(st, s->ix, s->pin_ix, s->ev_i0, s->ev_i1, d_words, n_words, graph_offset, I);
+      s->bytes_to_host += 40; s->st_index_ms = I.ms;
+      if(rc != ALD_OK) return rc; }
+    const int64_t nt = I.nt, ng = I.ng;
+    s->st_transcripts = nt; s->st_groups = ng;
+    DevBuf &d_len = s->sr[0], &d_at = s->sr[1], &d_keep = s->sr[2], &d_kord = s->sr[3], &d_tmp = s->sr[4], &d_covin = s->sr[5], &d_tidin = s->sr[6], &d_cov = s->sr[7], &d_tidk = s->sr[8];
+    // a scratch record has 6 words more than its transcript has in the stream (18 + k against 12 + k)
+    if(d_len.ensure(8 * (size_t)(nt + 1)) || d_at.ensure(8 * (size_t)(nt + 1)) || d_keep.ensure(4 * (size_t)(nt + 1)) || d_kord.ensure(4 * (size_t)(nt + 1))
+       || (coverage && (d_covin.ensure(8 * (size_t)nt) || d_cov.ensure(8 * (size_t)nt))) || (tid && (d_tidin.ensure(8 * (size_t)nt) || d_tidk.ensure(8 * (size_t)nt)))
+       || s->d_pool.ensure(4 * (size_t)(n_words + 6 * nt) + 64) || s->d_roff.ensure(8 * (size_t)nt + 8) || s->pin_sr.ensure(16 + 12 * (size_t)ng + 64)) return ald_set_err(ALD_ERR_NOMEM, "resident set stream buffers");
+    size_t b1 = 0, b2 = 0;
+    HCHK(hipcub::DeviceScan::ExclusiveSum(nullptr, b1, (const int64_t*)d_len.p, (int64_t*)d_at.p, (int)(nt + 1), st));
+    HCHK(hipcub::DeviceScan::ExclusiveSum(nullptr, b2, (const int32_t*)d_keep.p, (int32_t*)d_kord.p, (int)(nt + 1), st));
+    if(d_tmp.ensure(std::max(b1, b2) + 256)) return ald_set_err(ALD_ERR_NOMEM, "scan scratch");
+    if(coverage) HCHK(hipMemcpyAsync(d_covin.p, coverage, 8 * (size_t)nt, hipMemcpyHostToDevice, st));
+    if(tid) HCHK(hipMemcpyAsync(d_tidin.p, tid, 8 * (size_t)nt, hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(sr_len, dim3(grid_for(nt + 1)), dim3(TX_BLOCK), 0, st, d_words, I.toff, nt, (int)(skip_single_exon != 0), (int64_t*)d_len.p, (int32_t*)d_keep.p);
+    HCHK(hipcub::DeviceScan::ExclusiveSum(d_tmp.p, b1, (const int64_t*)d_len.p, (int64_t*)d_at.p, (int)(nt + 1), st));
+    HCHK(hipcub::DeviceScan::ExclusiveSum(d_tmp.p, b2, (const int32_t*)d_keep.p, (int32_t*)d_kord.p, (int)(nt + 1), st));
+    hipLaunchKernelGGL(sr_emit, dim3(grid_for(16 * nt)), dim3(TX_BLOCK), 0, st, d_words, I.toff, I.gid, (const int64_t*)d_at.p, (const int32_t*)d_kord.p, nt,
+                       coverage ? (const double*)d_covin.p : (const double*)nullptr, tid ? (const int64_t*)d_tidin.p : (const int64_t*)nullptr,
+                       (uint32_t*)s->d_pool.p, (unsigned long long*)s->d_roff.p, (double*)d_cov.p, (int64_t*)d_tidk.p);
+    // to the host: the number of kept transcripts, label + sid of every group (12 bytes per group)
+    char *hp = (char*)s->pin_sr.p; int64_t *h_label = (int64_t*)(hp + 16); int32_t *h_sid = (int32_t*)(hp + 16 + 8 * (size_t)ng);
+    HCHK(hipMemcpyAsync(hp, (const int32_t*)d_kord.p + nt, 4, hipMemcpyDeviceToHost, st));
+    HCHK(hipMemcpyAsync(h_label, I.label, 8 * (size_t)ng, hipMemcpyDeviceToHost, st));
+    HCHK(hipMemcpyAsync(h_sid, I.sid, 4 * (size_t)ng, hipMemcpyDeviceToHost, st));
+    HCHK(hipStreamSynchronize(st));
+    if(hipGetLastError() != hipSuccess) return ald_set_err(ALD_ERR_HIP, "a stream-record kernel failed to launch");
+    s->bytes_to_host += 4 + 12 * ng;
+    const int64_t np = (int64_t)*(const int32_t*)hp;
+    // without the filter every transcript is kept and a path's ordinal is its ordinal in the stream: coverage[] / tid[] serve the host part as they are
+    return add_records(s, (const uint32_t*)s->d_pool.p, (const unsigned long long*)s->d_roff.p, nullptr, nullptr, coverage, tid, np, (int)ng, h_sid, h_label, tid_base, skip_single_exon,
+                       coverage ? (const double*)d_cov.p : (const double*)nullptr, tid ? (const int64_t*)d_tidk.p : (const int64_t*)nullptr);
 }
 
 int has_device(int32_t device)
@@ -471,6 +562,7 @@ int ald_tset_dev_create(int32_t device, double single_exon_overlap, ald_tset_dev
     s->device = device;
     HCHK(hipStreamCreateWithFlags(&s->st, hipStreamNonBlocking));
     HCHK(hipEventCreate(&s->ev0)); HCHK(hipEventCreate(&s->ev1)); HCHK(hipEventCreateWithFlags(&s->ev_w, hipEventDisableTiming));
+    HCHK(hipEventCreate(&s->ev_i0)); HCHK(hipEventCreate(&s->ev_i1));
     *out = s.release();
     return ALD_OK;
 }
@@ -506,16 +598,22 @@ int ald_tset_dev_add_stream(ald_tset_dev *s, const uint32_t *words, int64_t n_wo
     if(!s || n_words < 0 || (n_words > 0 && !words)) return ALD_ERR_INVALID;
     const auto T0 = std::chrono::steady_clock::now();
     HCHK(hipSetDevice(s->device));
-    std::vector<uint32_t> staged;                           // a stream in device memory (e.g. one an RCCL gather left there) comes to the host first
-    hipPointerAttribute_t at;
-    if(n_words > 0 && hipPointerGetAttributes(&at, words) == hipSuccess && at.type == hipMemoryTypeDevice) {
+    s->st_transcripts = s->st_groups = s->st_words_to_host = s->bytes_to_host = 0; s->st_index_ms = 0;
+    const bool dev = n_words > 0 && tx_on_device(words);
+    if(dev && n_words < (int64_t)1 << 31) {                 // a stream in device memory (e.g. a segment the owner exchange left there) stays there
+        const int rc = add_device_stream(s, words, n_words, coverage, tid, graph_offset, tid_base, skip_single_exon);
+        s->last_call_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - T0).count();
+        return rc;
+    }
+    std::vector<uint32_t> staged;                           // 2^31 words or more: beyond the index's 32-bit nodes, it comes to the host for the walk
+    if(dev) {
         staged.resize((size_t)n_words);
         HCHK(hipMemcpy(staged.data(), words, 4 * (size_t)n_words, hipMemcpyDeviceToHost));
-        words = staged.data();
+        words = staged.data(); s->st_words_to_host = n_words; s->bytes_to_host += 4 * n_words;
     }
-    hipGetLastError();                                      // (a host pointer unknown to the runtime leaves an error behind)
     StreamRecords R;
     { int rc = tx_stream_records(words, n_words, coverage, tid, skip_single_exon, graph_offset, R); if(rc != ALD_OK) return rc; }
+    s->st_transcripts = R.n_transcripts; s->st_groups = (int64_t)R.label.size();
     const int64_t np = (int64_t)R.roff.size();
     if(np > 0) {
         if(s->d_pool.ensure(4 * R.pool.size() + 64) || s->d_roff.ensure(8 * (size_t)np + 8)) return ald_set_err(ALD_ERR_NOMEM, "resident set stream buffers");
@@ -526,6 +624,15 @@ int ald_tset_dev_add_stream(ald_tset_dev *s, const uint32_t *words, int64_t n_wo
                                np, (int)R.label.size(), R.sid.empty() ? nullptr : R.sid.data(), R.label.data(), tid_base, 0 /* filtered above */);
     s->last_call_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - T0).count();
     return rc;
+}
+
+int ald_tset_dev_stream_stats(const ald_tset_dev *s, int64_t *n_transcripts, int64_t *n_graphs, int64_t *words_to_host, int64_t *bytes_to_host, double *index_ms)
+{
+    if(!s) return ALD_ERR_INVALID;
+    if(n_transcripts) *n_transcripts = s->st_transcripts; if(n_graphs) *n_graphs = s->st_groups;
+    if(words_to_host) *words_to_host = s->st_words_to_host; if(bytes_to_host) *bytes_to_host = s->bytes_to_host;
+    if(index_ms) *index_ms = s->st_index_ms;
+    return ALD_OK;
 }
 
 int ald_tset_dev_merge(ald_tset_dev *dst, ald_tset_dev *src)

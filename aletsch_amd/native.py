@@ -242,6 +242,9 @@ def load_library():
     lib.ald_batch_device_transcript_streams_by_owner.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_void_p), C.POINTER(C.POINTER(C.c_int64))]
     lib.ald_transcript_bucket.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_uint64)]
     lib.ald_tset_split_stream.argtypes = [C.c_int32, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p]
+    if hasattr(lib, "ald_tset_index_stream"):            # (an older build named by ALETSCH_DECOMP_LIB for an A/B run has neither: calling them then raises AttributeError)
+        lib.ald_tset_index_stream.argtypes = [C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+        lib.ald_tset_dev_stream_stats.argtypes = [C.c_void_p] + [C.POINTER(C.c_int64)] * 4 + [C.POINTER(C.c_double)]
     lib.ald_records_add_graph_offset.argtypes = [C.c_void_p, C.c_int64, C.c_int32]
     lib.ald_tset_destroy.argtypes = [C.c_void_p]
     lib.ald_tset_create.argtypes = [C.c_double, C.POINTER(C.c_void_p)]
@@ -701,6 +704,24 @@ class DeviceTranscriptSet:
         _check(self._lib.ald_tset_dev_add_stream(self._h, C.c_void_p(words.ctypes.data), C.c_int64(words.size), cp, tp, C.c_int32(int(graph_offset)),
                                                  C.c_int64(int(tid_base)), C.c_int32(int(skip_single_exon))))
 
+    def add_stream_ptr(self, ptr: int, n_words: int, coverage=None, tid=None, graph_offset: int = 0, tid_base: int = 0, skip_single_exon: bool = False):
+        """add_stream on a raw pointer to n_words stream words in host or DEVICE memory (e.g. a segment the owner exchange left in HBM:
+        it is indexed and folded there, no word of it comes to the host); coverage / tid: host arrays, one per transcript of the stream."""
+        cp = tp = None
+        if coverage is not None:
+            coverage = np.ascontiguousarray(coverage, np.float64); cp = C.c_void_p(coverage.ctypes.data)
+        if tid is not None:
+            tid = np.ascontiguousarray(tid, np.int64); tp = C.c_void_p(tid.ctypes.data)
+        _check(self._lib.ald_tset_dev_add_stream(self._h, C.c_void_p(int(ptr)), C.c_int64(int(n_words)), cp, tp, C.c_int32(int(graph_offset)),
+                                                 C.c_int64(int(tid_base)), C.c_int32(int(skip_single_exon))))
+
+    def stream_stats(self):
+        """Of the last add_stream / add_stream_ptr (ald_tset_dev_stream_stats): transcripts and graphs of the stream, stream words and
+        all bytes copied device -> host, device milliseconds of the index kernels."""
+        v = [C.c_int64() for _ in range(4)]; ms = C.c_double()
+        _check(self._lib.ald_tset_dev_stream_stats(self._h, *[C.byref(x) for x in v], C.byref(ms)))
+        return dict(n_transcripts=v[0].value, n_graphs=v[1].value, words_to_host=v[2].value, bytes_to_host=v[3].value, index_ms=ms.value)
+
     def merge(self, other: "DeviceTranscriptSet"):
         """transcript_set::add(transcript_set&) on the device; `other` is left empty."""
         _check(self._lib.ald_tset_dev_merge(self._h, other._h))
@@ -774,6 +795,22 @@ def split_stream_into(src_ptr: int, n_words: int, world: int, dst_ptr: int, offs
     assert offsets.dtype == np.int64 and offsets.flags.c_contiguous and offsets.size >= max(int(world), 0) + 1
     _check(load_library().ald_tset_split_stream(C.c_int32(device), C.c_void_p(src_ptr), C.c_int64(n_words), C.c_int32(int(world)), C.c_void_p(dst_ptr), C.c_void_p(offsets.ctypes.data)))
     return offsets
+
+
+def index_stream_into(src_ptr: int, n_words: int, offsets, capacity: int, device: int = 0):
+    """ald_tset_index_stream on raw pointers: the transcript boundaries of a stream in host or device memory, found by kernels ->
+    (n_transcripts, n_graphs).  offsets: an int64 numpy array, a raw host or device pointer to `capacity` int64 entries, or None (counts only)."""
+    if isinstance(offsets, np.ndarray):
+        assert offsets.dtype == np.int64 and offsets.flags.c_contiguous and offsets.size >= capacity
+        op = C.c_void_p(offsets.ctypes.data)
+    else:
+        op = C.c_void_p(int(offsets)) if offsets else None
+    nt = C.c_int64(); ng = C.c_int64()
+    rc = load_library().ald_tset_index_stream(C.c_int32(device), C.c_void_p(int(src_ptr)) if src_ptr else None, C.c_int64(int(n_words)), op, C.c_int64(int(capacity)), C.byref(nt), C.byref(ng))
+    if rc != 0:
+        e = DecompError(rc, (load_library().ald_last_error() or b"").decode()); e.counts = (nt.value, ng.value)      # (the counts are filled in when only `capacity` was short)
+        raise e
+    return nt.value, ng.value
 
 
 def _two_pass(fn, *args) -> str:

@@ -362,9 +362,16 @@ int  ald_transcript_bucket(const int32_t *exon_lr, int32_t n_exons, uint64_t *ha
 int  ald_batch_device_transcript_streams_by_owner(const ald_batch *b, const int32_t *sid, int32_t skip_single_exon, int32_t world,
                                                   void **dev_words, const int64_t **offsets);
 /* the same split for a stream that already exists (host or device memory); out_words: caller's buffer of n_words words, host or
- * device; offsets: caller's [world + 1].  The record walk that finds the transcript boundaries runs on the host; owner, placement and
- * copy run in the kernels.  A malformed or non-ascending stream: ALD_ERR_INVALID, as in ald_tset_add_stream. */
+ * device; offsets: caller's [world + 1].  The transcript boundaries come from the stream index (ald_tset_index_stream), owner, placement
+ * and copy run in the kernels: a device stream never comes to the host (2^31 words or more: the boundaries are walked on the host).  A
+ * malformed or non-ascending stream: ALD_ERR_INVALID, as in ald_tset_add_stream. */
 int  ald_tset_split_stream(int32_t device, const uint32_t *words, int64_t n_words, int32_t world, uint32_t *out_words, int64_t *offsets);
+/* The transcript boundaries of a stream (format of ald_batch_transcript_stream), found by kernels: offsets[i] = first word of transcript i,
+ * offsets[n] = n_words.  words and offsets: host or device memory each; offsets may be NULL (counts only), else `capacity` entries
+ * (n_words / 12 + 2 always suffices; too few: ALD_ERR_INVALID with the counts filled in).  Malformed or descending: ALD_ERR_INVALID
+ * as in ald_tset_add_stream (2^31 words or more: ALD_ERR_INVALID as well).  No device: ALD_ERR_NO_DEVICE. */
+int  ald_tset_index_stream(int32_t device, const uint32_t *words, int64_t n_words, int64_t *offsets, int64_t capacity,
+                           int64_t *n_transcripts, int64_t *n_graphs);
 /* Merge such a stream, graph by graph in stream order (assembler.cc:1105-1133): coverage = log(1 + weight) is taken here, on the host;
  * tid = tid_base + ((graph + graph_offset) << 20 | path index), i.e. what ald_tset_add_batch gives the same graph in an unsharded batch */
 int  ald_tset_add_stream(ald_tset *t, const uint32_t *words, int64_t n_words, int32_t graph_offset, int64_t tid_base);
@@ -410,6 +417,12 @@ int  ald_tset_flat_free(ald_tset_flat *f);
  *   add_stream   == ald_tset_add_stream (stream format of ald_batch_transcript_stream; words in host or device memory).  coverage[i] /
  *                   tid[i] (optional, one per transcript of the stream): as ald_tset_reduce_stream; NULL: log(1 + weight) and
  *                   tid_base + ((graph + graph_offset) << 20 | path index).  Unlike ald_tset_add_stream it takes skip_single_exon.
+ *                   Words in DEVICE memory stay there: the boundaries come from the stream index, the records are built by a kernel, and
+ *                   per call at most 24 bytes per kept transcript, 16 per graph, the compacted records of the transcripts with fewer than
+ *                   two exons and a constant reach the host (2^31 words or more: the stream is copied to the host and walked there).  A
+ *                   refused stream (ALD_ERR_INVALID) leaves the set as it was.
+ *   stream_stats of the last add_stream: transcripts and graphs of the stream, stream words copied to host memory for a walk (0 on the
+ *                   device path), all bytes the call copied device -> host, device milliseconds of the index kernels (HIP events).
  *   merge        == ald_tset_merge (transcript_set::add(transcript_set&)): c_dst + c_src; src is left empty.
  *   size / export / snapshot   the items in the reference's iteration order (the arrays of ald_tset_export; snapshot: an ald_tset_flat
  *                   for ald_tset_flat_export / ald_tset_add_flat).
@@ -428,6 +441,10 @@ int  ald_tset_dev_export(const ald_tset_dev *s, uint64_t *hash, int32_t *count, 
                          int64_t *sample_offset, int32_t *sample_sid, double *sample_cov2, double *sample_conf, double *sample_abd, int32_t *sample_count1);
 int  ald_tset_dev_snapshot(const ald_tset_dev *s, ald_tset_flat **out);
 int  ald_tset_dev_stats(const ald_tset_dev *s, double *last_device_ms, double *last_call_ms, int64_t *device_items, int64_t *host_items);
+/* of the last ald_tset_dev_add_stream on this set: transcripts and groups of the stream, stream words copied to host memory for a walk
+ * (0 on the device path), all bytes the call copied device -> host, device milliseconds of the index kernels (HIP events) */
+int  ald_tset_dev_stream_stats(const ald_tset_dev *s, int64_t *n_transcripts, int64_t *n_graphs, int64_t *words_to_host,
+                               int64_t *bytes_to_host, double *index_ms);
 
 /* ---- the exchange step for a multi-PROCESS host (one process per MI355X): transcript streams -> rank 0 over RCCL / xGMI ----
  * (A host that drives all its devices from one process -- aletsch::gpu_assembly_queue over a device list -- needs none of this.)
