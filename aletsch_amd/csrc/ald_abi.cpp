@@ -5,6 +5,7 @@
 // packed path records that come back.  There is NO CPU compute path here: without a HIP device every compute
 // entry point fails with ALD_ERR_NO_DEVICE.
 #include "ald_internal.h"
+#include "tset_front.h"          // tx_walk_stream
 #include <thread>
 #include <chrono>
 #include <iterator>
@@ -317,10 +318,7 @@ int ald_batch_destroy(ald_batch *b)
     DevBuf *bufs[] = {&b->d_in, &b->d_status, &b->d_npaths, &b->d_niters, &b->d_pool, &b->d_poolused, &b->d_index, &b->d_gfirst, &b->d_pbegin, &b->d_ordoff, &b->d_trace_n, &b->d_trace_codes, &b->d_trace_vals, &b->d_work, &b->d_counter, &b->d_args};
     for(DevBuf *d : bufs) d->release();
     for(int c = 0; c < ALD_NUM_SLOTS; c++) b->d_slabs[c].release();
-    for(DevBuf &d : b->red) d.release();
-    for(DevBuf &d : b->dts) d.release();
-    for(DevBuf &d : b->tp) d.release();
-    for(PinBuf &d : b->red_pin) d.release();
+    b->tx.release(); b->tp.release(); b->d_ts_len.release(); b->d_ts_at.release(); b->d_ts_out.release();
     b->feat.release();
     for(int q = 0; q < ALD_SIDE_STREAMS_MAX; q++) if(b->cstream[q]) { hipStreamSynchronize(b->cstream[q]); hipStreamDestroy(b->cstream[q]); }
     for(int c = 0; c < ALD_NUM_SLOTS; c++) if(b->cdone[c]) hipEventDestroy(b->cdone[c]);
@@ -993,16 +991,10 @@ int ald_tset_add_stream(ald_tset *t, const uint32_t *words, int64_t n_words, int
     const auto T0 = std::chrono::steady_clock::now();
     // record boundaries and groups (one serial walk: the lengths are in the records)
     std::vector<int64_t> offs, grp; std::vector<int32_t> grp_sid;
-    int64_t last_graph = -1;
-    for(int64_t o = 0; o < n_words; ) {
-        if(o + TS_HDR > n_words) return set_err(ALD_ERR_INVALID, "malformed transcript stream");
-        const int64_t len = TS_HDR + 2 * (int64_t)words[o + 5];
-        if(o + len > n_words || (int32_t)words[o + 5] < 0) return set_err(ALD_ERR_INVALID, "malformed transcript stream");
-        const int64_t g = (int64_t)words[o];
-        if(g < last_graph) return set_err(ALD_ERR_INVALID, "transcript stream not in ascending graph order");
-        if(g != last_graph) { grp.push_back((int64_t)offs.size()); grp_sid.push_back((int32_t)words[o + 2]); last_graph = g; }
-        offs.push_back(o); o += len;
-    }
+    { int rc = tx_walk_stream(words, n_words, [&](int64_t o, bool first) {
+          if(first) { grp.push_back((int64_t)offs.size()); grp_sid.push_back((int32_t)words[o + 2]); }
+          offs.push_back(o);
+      }); if(rc != ALD_OK) return rc; }
     const int64_t nt = (int64_t)offs.size(); grp.push_back(nt);
     const unsigned nthr = sink_threads(nt);
     const auto T1 = std::chrono::steady_clock::now();

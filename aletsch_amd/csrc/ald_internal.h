@@ -46,6 +46,74 @@ struct FeatTable {
                      h_rows.release(); h_complete.release(); h_rc.release(); if(e0) hipEventDestroy(e0); if(e1) hipEventDestroy(e1); e0 = e1 = nullptr; valid = false; }
 };
 
+// ---- scratch of the transcript-set side (tset_*.hip), one named buffer per role.  Kept by an owner across calls (a batch, a resident set)
+// or temporary for one entry point (tset_front.h: Scoped<>); every struct frees what it holds in release().
+
+// The front end of a batch's transcripts (tset_reduce.hip: tx_front_*).  "per path" = in (graph, path) order, "per place" = in sorted order.
+// What a front end run leaves behind for its caller: cov, weight, key_sorted, sidx, head, gid, groups, samples.
+// A batch's own (ald_batch::tx) is also borrowed by name, outside any reduction, by device_path_table (cub_tmp), the device transcript
+// stream (sid, cub_tmp, p_count) and the owner split (sid): all of them enqueue on ald_batch::stream, which is what orders them against
+// the reduction and against each other.
+struct TxScratch {
+    DevBuf single_len, single_at;      // tx_compact_singles: record length / first word of every single-exon record
+    DevBuf cov, weight;                // per path: coverage; the record's weight (only when the coverages are made from the records)
+    DevBuf nw, graph;                  // per path: exon words, graph
+    DevBuf key;                        // per path: group key.  Second life (tx_front_fold): (group, sample) key per place, unsorted
+    DevBuf key_sorted;                 // per place: group key, sorted
+    DevBuf idx;                        // per path: its ordinal, the sort's value input.  Second life (tx_front_fold): the (group, sample) keys, sorted
+    DevBuf sidx;                       // per place: path
+    DevBuf sid;                        // per graph: sample id (the caller's, uploaded)
+    DevBuf head, gid;                  // per place: first of its group?  1-based group id
+    DevBuf groups;                     // TxGroup[n_groups]
+    DevBuf cub_tmp;                    // hipCUB temporary storage (tx_cub)
+    DevBuf run_head, run_id;           // per (group, sample)-sorted place: first of its run?  1-based run id
+    DevBuf samples;                    // TxSample[n_runs], sorted by group, then sample id
+    DevBuf pos, pos_sorted;            // places 0 .. n_dev - 1, and the same in (group, sample) order
+    PinBuf p_key, p_groups, p_samples; // host copies: sorted group keys, TxGroup[], TxSample[]
+    PinBuf p_count;                    // a few counters (merge path of a resident set; length of a batch's device stream)
+    PinBuf p_weight, p_cov;            // per path: weights from the records, the coverages tx_front_coverage makes of them
+    PinBuf p_single_off, p_single_words;   // tx_compact_singles: offsets and words of the compacted records
+    void release() { DevBuf *d[] = {&single_len, &single_at, &cov, &weight, &nw, &graph, &key, &key_sorted, &idx, &sidx, &sid, &head, &gid, &groups, &cub_tmp, &run_head, &run_id, &samples, &pos, &pos_sorted};
+                     PinBuf *p[] = {&p_key, &p_groups, &p_samples, &p_count, &p_weight, &p_cov, &p_single_off, &p_single_words};
+                     for(DevBuf *x : d) x->release(); for(PinBuf *x : p) x->release(); }
+};
+// The merge path of a resident set (tset_resident.hip).  Incoming item = a batch's group or an item of a second set, in (hash, compare1) order.
+struct MergeScratch {
+    DevBuf ghead, perm;                // per group: head place; groups in (bucket, compare1) order
+    DevBuf match, ins, unm, start;     // per incoming item: resident item it lands on or -1, insertion point, 1 = new; per group: match (tx_fold's start)
+    DevBuf ub, cnt, shift, rmatch;     // exclusive scan of unm; per resident item: new items placed in front, its inclusive scan, the incoming item landing on it
+    DevBuf slot, ecnt, scnt;           // per output item: source, exons, samples
+    DevBuf sbeg;                       // per group: first sample run
+    DevBuf singles;                    // the compacted single-exon records of a finished batch (tx_compact_singles)
+    DevBuf cub_tmp;
+    void release() { DevBuf *d[] = {&ghead, &perm, &match, &ins, &unm, &start, &ub, &cnt, &shift, &rmatch, &slot, &ecnt, &scnt, &sbeg, &singles, &cub_tmp}; for(DevBuf *x : d) x->release(); }
+};
+// A device stream turned into scratch records (tset_resident.hip: sr_len / sr_emit).  Per transcript of the stream unless said otherwise.
+struct StreamRecScratch {
+    DevBuf len, at, keep, kord;        // words of its record (0: left out), first word, 1 = kept, ordinal among the kept
+    DevBuf cov_in, tid_in, cov, tid;   // the caller's coverage / tid by stream ordinal (uploaded), and gathered to the kept ordinal
+    DevBuf cub_tmp;
+    PinBuf p_head;                     // number of kept transcripts, then label and sid of every group
+    void release() { DevBuf *d[] = {&len, &at, &keep, &kord, &cov_in, &tid_in, &cov, &tid, &cub_tmp}; for(DevBuf *x : d) x->release(); p_head.release(); }
+};
+// The stream index (tset_index.hip: tx_stream_index).  toff, gid, label, sid are its results and live here until the next call.
+struct StreamIndexScratch {
+    DevBuf succ, succ_next, mark;      // per node: successor (two buffers, swapped every round of doubling), reached from position 0?
+    DevBuf toff, head, gid;            // per transcript: first word (+ one entry: n_words), first of its run of equal graph ids?  1-based run
+    DevBuf label, sid;                 // per run: graph id + graph_offset, sample id
+    DevBuf sum, cub_tmp;               // counts + flags (ix_graphs)
+    PinBuf p_sum;
+    void release() { DevBuf *d[] = {&succ, &succ_next, &mark, &toff, &head, &gid, &label, &sid, &sum, &cub_tmp}; for(DevBuf *x : d) x->release(); p_sum.release(); }
+};
+// The owner split (tset_partition.hip).  "sorted" = stable by owner.
+struct OwnerSplitScratch {
+    DevBuf owner, owner_sorted, ord, ord_sorted;   // per transcript: owner, ordinal; the same sorted
+    DevBuf len, len_sorted, place;     // per transcript: words; per sorted place: words of the transcript that lands there, its first word (+ one entry: the total)
+    DevBuf offsets, cub_tmp;           // first word of every owner's sub-stream (+ the total)
+    DevBuf out;                        // the sub-streams, back to back (the stream entry point uses it only when the caller's buffer is on the host)
+    void release() { DevBuf *d[] = {&owner, &owner_sorted, &ord, &ord_sorted, &len, &len_sorted, &place, &offsets, &cub_tmp, &out}; for(DevBuf *x : d) x->release(); }
+};
+
 struct ald_batch {
     int device = 0; int n_cus = 0;
     Params prm;
@@ -89,9 +157,9 @@ struct ald_batch {
     int passes = 0;
     const void *launched_slab[ALD_NUM_SLOTS] = {};      // test hook (ald_batch_debug_slab)
     rvec<uint32_t> tstream;                                // last transcript stream built from this batch (ald_batch_transcript_stream)
-    DevBuf red[20]; PinBuf red_pin[8];                     // scratch of ald_batch_reduce_transcripts, kept across calls (tset_reduce.hip)
-    DevBuf dts[3];                                         // ald_batch_device_transcript_stream: lengths / offsets / the stream itself
-    DevBuf tp[10]; std::vector<int64_t> tp_offsets;        // ald_batch_device_transcript_streams_by_owner (tset_partition.hip): scratch, the sub-streams, their offsets
+    TxScratch tx;                                          // scratch of ald_batch_reduce_transcripts, kept across calls (tset_reduce.hip)
+    DevBuf d_ts_len, d_ts_at, d_ts_out;                    // ald_batch_device_transcript_stream: lengths (also device_path_table's) / offsets / the stream itself
+    OwnerSplitScratch tp; std::vector<int64_t> tp_offsets; // ald_batch_device_transcript_streams_by_owner (tset_partition.hip): scratch + the sub-streams, their offsets
     FeatTable feat;                                        // ald_batch_features_all
 };
 

@@ -40,8 +40,30 @@ struct TxSample { int32_t gid, sid, count1, pad; double cov2, conf, abd; };
 
 // scratch of a front end run (owned by a batch or a resident set and kept across calls, or temporary for the stream entry point)
 // d2h (optional): every byte the front end copies device -> host is added to it (ald_tset_dev_stream_stats)
-struct RedScratch { DevBuf *red; PinBuf *pin; hipStream_t st; int64_t *d2h = nullptr; };
+struct RedScratch { TxScratch *x; hipStream_t st; int64_t *d2h = nullptr; };
 inline void tx_count_d2h(const RedScratch &S, size_t bytes) { if(S.d2h) *S.d2h += (int64_t)bytes; }
+// what a temporary owner holds for one call: scratch (anything with release()), a stream, a pair of events -- gone on scope exit
+template<class T> struct Scoped : T { ~Scoped() { this->release(); } };
+struct ScopedStream { hipStream_t s = nullptr; ~ScopedStream() { if(s) hipStreamDestroy(s); } };
+struct EventPair { hipEvent_t a = nullptr, b = nullptr; ~EventPair() { if(a) hipEventDestroy(a); if(b) hipEventDestroy(b); } };
+// a visible HIP device of that index, or the error an entry point returns without one.  who: the caller's noun ("the reduction")
+inline int tx_need_device(int32_t device, const char *who)
+{
+    int ndev = 0;
+    if(hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return ald_set_err(ALD_ERR_NO_DEVICE, std::string("no HIP device visible: ") + who + " has no CPU fallback");
+    if(device < 0 || device >= ndev) return ald_set_err(ALD_ERR_INVALID, "device index out of range");
+    return ALD_OK;
+}
+// The hipCUB two-step: call(null, bytes) asks for the temporary storage, tmp grows to it, call(tmp.p, bytes) enqueues the work.
+// call(void *tmp, size_t &bytes) -> hipError_t.  A growth of tmp frees the old block, which waits for the device: safe between enqueued
+// work, and it only happens on an input larger than any before.
+template<class F> int tx_cub(DevBuf &tmp, const char *what, F call)
+{
+    size_t bytes = 0;
+    hipError_t e = call(nullptr, bytes);
+    if(e == hipSuccess) { if(tmp.ensure(bytes + 256)) return ald_set_err(ALD_ERR_NOMEM, what); e = call(tmp.p, bytes); }
+    return e == hipSuccess ? ALD_OK : ald_set_err(ALD_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
+}
 // is p device memory?  (a plain host pointer makes the query fail: not an error here)
 inline bool tx_on_device(const void *p)
 {
@@ -50,37 +72,36 @@ inline bool tx_on_device(const void *p)
     return dev;
 }
 
-// What the front end leaves behind.  In S.red: [2] coverage per path, [3] weight per path (tx_front_sort without h_cov), [6] sorted group keys, [7] sorted (group, sample) keys,
-// [8] path of every sorted position (sidx), [11] head flags, [12] 1-based group id of every sorted position, [13] TxGroup[n_groups],
-// [17] TxSample[n_runs] (sorted by group, then sample id).  host_paths: the transcripts with fewer than two exons, (graph, path) order.
+// What the front end leaves behind: TxScratch's cov, weight, key_sorted, sidx, head, gid, groups, samples (ald_internal.h says what each
+// holds).  host_paths: the transcripts with fewer than two exons, (graph, path) order.
 // ev0 (optional): recorded once the inputs are on the device, i.e. where the device time of the caller's section begins.
 // ev_w / h_cov: only when the coverages are made from the records (tx_front_sort without h_cov): the event behind the D2H of the weights,
-// and the coverages tx_front_coverage computed (pinned, S.pin[5]).
+// and the coverages tx_front_coverage computed (pinned, p_cov).
 // d_cov (set by the caller, optional): coverage per path already in DEVICE memory (a device stream folded with the caller's coverages):
 // tx_front_sort without h_cov then copies it device to device and neither fetches the weights nor needs tx_front_coverage.
 struct TxFront { int64_t np = 0, n_dev = 0; int32_t n_groups = 0, n_runs = 0; std::vector<int64_t> host_paths; hipEvent_t ev0 = nullptr; bool sid_on_device = false;
                  hipEvent_t ev_w = nullptr; const double *h_cov = nullptr; const double *d_cov = nullptr; };
-inline const uint64_t *tx_skey(const RedScratch &S) { return (const uint64_t*)S.red[6].p; }
-inline const int64_t *tx_sidx(const RedScratch &S) { return (const int64_t*)S.red[8].p; }
-inline const int32_t *tx_head(const RedScratch &S) { return (const int32_t*)S.red[11].p; }
-inline const int32_t *tx_gid(const RedScratch &S) { return (const int32_t*)S.red[12].p; }
-inline TxGroup *tx_groups(const RedScratch &S) { return (TxGroup*)S.red[13].p; }
-inline TxSample *tx_samples(const RedScratch &S) { return (TxSample*)S.red[17].p; }
+inline const uint64_t *tx_skey(const RedScratch &S) { return (const uint64_t*)S.x->key_sorted.p; }
+inline const int64_t *tx_sidx(const RedScratch &S) { return (const int64_t*)S.x->sidx.p; }
+inline const int32_t *tx_head(const RedScratch &S) { return (const int32_t*)S.x->head.p; }
+inline const int32_t *tx_gid(const RedScratch &S) { return (const int32_t*)S.x->gid.p; }
+inline TxGroup *tx_groups(const RedScratch &S) { return (TxGroup*)S.x->groups.p; }
+inline TxSample *tx_samples(const RedScratch &S) { return (TxSample*)S.x->samples.p; }
 
 // exon join / bucket hash / stable sort by group / head flags / group ids: F.n_dev, F.n_groups, F.host_paths.  h_cov: coverage per path
 // (host libm), sid: sample per graph or null.  Enqueued on S.st; returns after the counts are on the host.
 int tx_front_groups(RedScratch S, TxIn in, const double *h_cov, int n_graphs, const int32_t *sid, TxFront &F);
 // tx_front_groups in its two halves, for a caller without a host copy of the records (a batch that ald_batch_finish ended):
 //   tx_front_sort      keys + the stable sort, ENQUEUED only.  h_cov = null: the key pass also writes weight[p] (record word 6) into a dense
-//                      array in (graph, path) order (S.red[3]), 8 bytes per path go to pinned memory (S.pin[4]) and F.ev_w is recorded
+//                      array in (graph, path) order (weight), 8 bytes per path go to pinned memory (p_weight) and F.ev_w is recorded
 //   tx_front_coverage  waits for F.ev_w, takes log(1 + w) with the host's libm on up to 16 threads (ALD_SINK_THREADS) WHILE THE SORT RUNS, and
-//                      enqueues the upload to where tx_front_groups puts h_cov (S.red[2]): coverage is first read by tx_fold
+//                      enqueues the upload to where tx_front_groups puts h_cov (cov): coverage is first read by tx_fold
 //   tx_front_heads     waits for the sort; head flags, group ids, F.n_dev / n_groups / host_paths
 int tx_front_sort(RedScratch S, TxIn in, const double *h_cov, int n_graphs, const int32_t *sid, TxFront &F);
 int tx_front_coverage(RedScratch S, TxFront &F);
 int tx_front_heads(RedScratch S, TxIn in, TxFront &F);
 // The records of F.host_paths (fewer than two exons) compacted on the device -- lengths, exclusive scan, a 16-lane copy per record into
-// d_out -- and brought to pinned memory (S.pin[6]: offsets, S.pin[7]: words): *h_words + (*h_off)[a] is the record of F.host_paths[a].
+// d_out -- and brought to pinned memory (p_single_off, p_single_words): *h_words + (*h_off)[a] is the record of F.host_paths[a].
 // Enqueued on S.st; the caller waits for the stream before it reads them.
 int tx_compact_singles(RedScratch S, TxIn in, const TxFront &F, DevBuf &d_out, const uint32_t **h_words, const unsigned long long **h_off);
 // the fold of every group (tx_fold) and its per-sample runs (tx_sfold).  start_idx[group] >= 0: the group lands on a resident item whose
@@ -93,16 +114,31 @@ void tx_host_singles(aletsch::transcript_sink &into, const std::vector<int64_t> 
 // a transcript stream (format of ald_batch_transcript_stream) turned into records the front end reads
 struct StreamRecords { std::vector<uint32_t> pool; std::vector<unsigned long long> roff; std::vector<double> cov; std::vector<int32_t> sid; std::vector<int64_t> label, tids; int64_t n_transcripts = 0; };
 int tx_stream_records(const uint32_t *words, int64_t n_words, const double *coverage, const int64_t *tid, int32_t skip_single_exon, int64_t graph_offset, StreamRecords &R);
+// The host walk over the transcript boundaries of a stream: each(o, first) for the transcript at word o, first = it begins a run of equal
+// graph ids.  A header or record that does not fit, a negative exon count, a descending graph id: ALD_ERR_INVALID.
+template<class F> int tx_walk_stream(const uint32_t *words, int64_t n_words, F each)
+{
+    int64_t last = -1;
+    for(int64_t o = 0; o < n_words; ) {
+        if(o + ALD_TS_HDR > n_words) return ald_set_err(ALD_ERR_INVALID, "malformed transcript stream");
+        const int64_t len = ALD_TS_HDR + 2 * (int64_t)words[o + 5];
+        if((int32_t)words[o + 5] < 0 || o + len > n_words) return ald_set_err(ALD_ERR_INVALID, "malformed transcript stream");
+        const int64_t g = (int64_t)words[o];
+        if(g < last) return ald_set_err(ALD_ERR_INVALID, "transcript stream not in ascending graph order");
+        each(o, g != last);
+        last = g; o += len;
+    }
+    return ALD_OK;
+}
 // The same walk on the device (tset_index.hip): the transcript boundaries of a stream in DEVICE memory by pointer doubling over the record
 // lengths.  toff[i] = first word of transcript i, toff[nt] = n_words; gid[i] = 1-based run of equal graph ids transcript i belongs to
 // (runs counted before any single-exon filter, as tx_stream_records pushes label / sid before it skips); label[k] = graph id of run k +
-// graph_offset, sid[k] = word 2 of its first transcript.  All four live in ix[] (the caller's, IX_BUFS DevBufs) until the next call.
-// Kernels on `st`; ONE copy of 40 bytes (counts + flags, into `pin`) and one synchronisation.  e0 / e1 (optional): recorded around the
+// graph_offset, sid[k] = word 2 of its first transcript.  All four live in X (the caller's) until the next call.
+// Kernels on `st`; ONE copy of 40 bytes (counts + flags, into X.p_sum) and one synchronisation.  e0 / e1 (optional): recorded around the
 // kernels, ms = the time between them.  Malformed or descending: ALD_ERR_INVALID as tx_stream_records; n_words == 0 launches nothing;
 // n_words >= 2^31: ALD_ERR_INVALID (the callers keep the host walk for such a stream).
-enum { IX_BUFS = 10 };
 struct StreamIndex { const unsigned long long *toff = nullptr; const int32_t *gid = nullptr; const int64_t *label = nullptr; const int32_t *sid = nullptr; int64_t nt = 0, ng = 0; double ms = 0; };
-int tx_stream_index(hipStream_t st, DevBuf *ix, PinBuf &pin, hipEvent_t e0, hipEvent_t e1, const uint32_t *d_words, int64_t n_words, int64_t graph_offset, StreamIndex &I);
+int tx_stream_index(hipStream_t st, StreamIndexScratch &X, hipEvent_t e0, hipEvent_t e1, const uint32_t *d_words, int64_t n_words, int64_t graph_offset, StreamIndex &I);
 // the path table of a downloaded or finished batch in (graph, path) order on the device (b->d_ordoff), built once per run
 int device_path_table(ald_batch *b);
 

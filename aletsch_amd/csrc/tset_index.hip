@@ -83,31 +83,28 @@ __global__ void ix_labels(const uint32_t *words, int64_t n_words, const unsigned
 
 } // namespace
 
-int tx_stream_index(hipStream_t st, DevBuf *ix, PinBuf &pin, hipEvent_t e0, hipEvent_t e1, const uint32_t *d_words, int64_t n_words, int64_t graph_offset, StreamIndex &I)
+int tx_stream_index(hipStream_t st, StreamIndexScratch &X, hipEvent_t e0, hipEvent_t e1, const uint32_t *d_words, int64_t n_words, int64_t graph_offset, StreamIndex &I)
 {
     I = StreamIndex();
     if(n_words <= 0) return ALD_OK;
     if(n_words >= (int64_t)1 << 31) return ald_set_err(ALD_ERR_INVALID, "stream index: 2^31 words or more");
     const uint32_t M = (uint32_t)((n_words + 1) / 2); const int64_t N = (int64_t)M + 2, cap = n_words / ALD_TS_HDR + 1;
-    DevBuf &d_a = ix[0], &d_b = ix[1], &d_mark = ix[2], &d_toff = ix[3], &d_head = ix[4], &d_gid = ix[5], &d_label = ix[6], &d_sid = ix[7], &d_tmp = ix[8], &d_sum = ix[9];
+    DevBuf &d_a = X.succ, &d_b = X.succ_next, &d_mark = X.mark, &d_toff = X.toff, &d_head = X.head, &d_gid = X.gid, &d_label = X.label, &d_sid = X.sid, &d_tmp = X.cub_tmp, &d_sum = X.sum;
+    PinBuf &pin = X.p_sum;
     if(d_a.ensure(4 * (size_t)N) || d_b.ensure(4 * (size_t)N) || d_mark.ensure((size_t)N) || d_toff.ensure(8 * (size_t)(cap + 1)) || d_head.ensure(4 * (size_t)cap) || d_gid.ensure(4 * (size_t)cap)
        || d_label.ensure(8 * (size_t)cap) || d_sid.ensure(4 * (size_t)cap) || d_sum.ensure(64) || pin.ensure(64)) return ald_set_err(ALD_ERR_NOMEM, "stream index buffers");
     hipcub::CountingInputIterator<unsigned long long> count(0);
     hipcub::TransformInputIterator<unsigned long long, IxTwice, hipcub::CountingInputIterator<unsigned long long>> pos(count, IxTwice());
     unsigned long long *sum = (unsigned long long*)d_sum.p;
-    size_t sel_bytes = 0, scan_bytes = 0;
-    HCHK(hipcub::DeviceSelect::Flagged(nullptr, sel_bytes, pos, (const uint8_t*)d_mark.p, (unsigned long long*)d_toff.p, sum, (int)M, st));
-    HCHK(hipcub::DeviceScan::InclusiveSum(nullptr, scan_bytes, (const int32_t*)d_head.p, (int32_t*)d_gid.p, (int)cap, st));
-    if(d_tmp.ensure(std::max(sel_bytes, scan_bytes) + 256)) return ald_set_err(ALD_ERR_NOMEM, "stream index scratch");
     int rounds = 0; while(((int64_t)1 << rounds) <= cap) rounds++;          // 2^rounds - 1 >= cap = the most links a chain can have
     if(e0) HCHK(hipEventRecord(e0, st));
     HCHK(hipMemsetAsync(d_sum.p, 0, 64, st));
     hipLaunchKernelGGL(ix_succ, dim3(grid_for(N)), dim3(TX_BLOCK), 0, st, d_words, n_words, M, (uint32_t*)d_a.p, (uint8_t*)d_mark.p);
     uint32_t *cur = (uint32_t*)d_a.p, *nxt = (uint32_t*)d_b.p;
     for(int r = 0; r < rounds; r++) { hipLaunchKernelGGL(ix_jump, dim3(grid_for(N)), dim3(TX_BLOCK), 0, st, (const uint32_t*)cur, nxt, (uint8_t*)d_mark.p, (uint32_t)N); std::swap(cur, nxt); }
-    HCHK(hipcub::DeviceSelect::Flagged(d_tmp.p, sel_bytes, pos, (const uint8_t*)d_mark.p, (unsigned long long*)d_toff.p, sum, (int)M, st));
+    { int rc = tx_cub(d_tmp, "stream index scratch", [&](void *t, size_t &nb) { return hipcub::DeviceSelect::Flagged(t, nb, pos, (const uint8_t*)d_mark.p, (unsigned long long*)d_toff.p, sum, (int)M, st); }); if(rc != ALD_OK) return rc; }
     hipLaunchKernelGGL(ix_graphs, dim3(grid_for(cap)), dim3(TX_BLOCK), 0, st, d_words, n_words, (unsigned long long*)d_toff.p, cap, sum, (int32_t*)d_head.p);
-    HCHK(hipcub::DeviceScan::InclusiveSum(d_tmp.p, scan_bytes, (const int32_t*)d_head.p, (int32_t*)d_gid.p, (int)cap, st));
+    { int rc = tx_cub(d_tmp, "stream index scratch", [&](void *t, size_t &nb) { return hipcub::DeviceScan::InclusiveSum(t, nb, (const int32_t*)d_head.p, (int32_t*)d_gid.p, (int)cap, st); }); if(rc != ALD_OK) return rc; }
     hipLaunchKernelGGL(ix_labels, dim3(grid_for(cap)), dim3(TX_BLOCK), 0, st, d_words, n_words, (const unsigned long long*)d_toff.p, cap, (const int32_t*)d_head.p, (const int32_t*)d_gid.p,
                        (const uint8_t*)d_mark.p, M, graph_offset, sum, (int64_t*)d_label.p, (int32_t*)d_sid.p);
     if(e1) HCHK(hipEventRecord(e1, st));
@@ -128,9 +125,7 @@ extern "C" {
 int ald_tset_index_stream(int32_t device, const uint32_t *words, int64_t n_words, int64_t *offsets, int64_t capacity, int64_t *n_transcripts, int64_t *n_graphs)
 {
     if(n_words < 0 || (n_words > 0 && !words) || (offsets && capacity < 0)) return ALD_ERR_INVALID;
-    int ndev = 0;
-    if(hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return ald_set_err(ALD_ERR_NO_DEVICE, "no HIP device visible: the stream index has no CPU fallback");
-    if(device < 0 || device >= ndev) return ald_set_err(ALD_ERR_INVALID, "device index out of range");
+    { int rc = tx_need_device(device, "the stream index"); if(rc != ALD_OK) return rc; }
     HCHK(hipSetDevice(device));
     if(n_transcripts) *n_transcripts = 0; if(n_graphs) *n_graphs = 0;
     const bool src_dev = tx_on_device(words), dst_dev = tx_on_device(offsets);
@@ -140,14 +135,13 @@ int ald_tset_index_stream(int32_t device, const uint32_t *words, int64_t n_words
         if(offsets) { if(dst_dev) HCHK(hipMemcpy(offsets, &zero, 8, hipMemcpyHostToDevice)); else offsets[0] = 0; }
         return ALD_OK;
     }
-    DevBuf ix[IX_BUFS], d_in; PinBuf pin;
-    struct Rel { DevBuf *x, *a; PinBuf *p; ~Rel() { for(int i = 0; i < IX_BUFS; i++) x[i].release(); a->release(); p->release(); } } rel{ix, &d_in, &pin};
-    hipStream_t st = nullptr; HCHK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-    struct StRel { hipStream_t s; ~StRel() { hipStreamDestroy(s); } } strel{st};
+    Scoped<StreamIndexScratch> ix; Scoped<DevBuf> d_in;
+    ScopedStream stream; HCHK(hipStreamCreateWithFlags(&stream.s, hipStreamNonBlocking));
+    hipStream_t st = stream.s;
     if(n_words >= (int64_t)1 << 31) return ald_set_err(ALD_ERR_INVALID, "stream index: 2^31 words or more");
     if(!src_dev) { if(d_in.ensure(4 * (size_t)n_words)) return ald_set_err(ALD_ERR_NOMEM, "stream index buffers"); HCHK(hipMemcpyAsync(d_in.p, words, 4 * (size_t)n_words, hipMemcpyHostToDevice, st)); }
     StreamIndex I;
-    const int rc = tx_stream_index(st, ix, pin, nullptr, nullptr, src_dev ? words : (const uint32_t*)d_in.p, n_words, 0, I);
+    const int rc = tx_stream_index(st, ix, nullptr, nullptr, src_dev ? words : (const uint32_t*)d_in.p, n_words, 0, I);
     if(rc != ALD_OK) return rc;
     if(n_transcripts) *n_transcripts = I.nt; if(n_graphs) *n_graphs = I.ng;
     if(offsets) {

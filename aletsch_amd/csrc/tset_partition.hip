@@ -69,34 +69,27 @@ template<bool REC> __global__ void tp_emit(TpSrc s, const int32_t *sord, const i
     for(int q = l; q < k; q += 16) w[ALD_TS_HDR + q] = x[q];
 }
 
-// scratch of one split: [0] owner, [1] sorted owner, [2] ordinal, [3] sorted ordinal, [4] length, [5] sorted length, [6] place, [7] sort / scan scratch, [8] offsets
-enum { TP_BUFS = 9 };
-
 // owner, stable sort, placement; h_offsets[world + 1] is on the host on return
-template<bool REC> int tp_place(hipStream_t st, DevBuf *tp, TpSrc s, int skip_single, int world, int64_t *h_offsets)
+template<bool REC> int tp_place(hipStream_t st, OwnerSplitScratch &T, TpSrc s, int skip_single, int world, int64_t *h_offsets)
 {
     const int64_t n = s.n;
     if(n >= (int64_t)1 << 31) return ald_set_err(ALD_ERR_INVALID, "owner split: more than 2^31 - 1 transcripts");
-    if(tp[0].ensure(4 * (size_t)n) || tp[1].ensure(4 * (size_t)n) || tp[2].ensure(4 * (size_t)n) || tp[3].ensure(4 * (size_t)n) || tp[4].ensure(4 * (size_t)n)
-       || tp[5].ensure(8 * (size_t)n + 8) || tp[6].ensure(8 * (size_t)n + 8) || tp[8].ensure(8 * (size_t)(world + 1))) return ald_set_err(ALD_ERR_NOMEM, "owner split buffers");
+    if(T.owner.ensure(4 * (size_t)n) || T.owner_sorted.ensure(4 * (size_t)n) || T.ord.ensure(4 * (size_t)n) || T.ord_sorted.ensure(4 * (size_t)n) || T.len.ensure(4 * (size_t)n)
+       || T.len_sorted.ensure(8 * (size_t)n + 8) || T.place.ensure(8 * (size_t)n + 8) || T.offsets.ensure(8 * (size_t)(world + 1))) return ald_set_err(ALD_ERR_NOMEM, "owner split buffers");
     int bits = 1; while((1 << bits) < world) bits++;
-    size_t sort_bytes = 0, scan_bytes = 0;
-    HCHK(hipcub::DeviceRadixSort::SortPairs(nullptr, sort_bytes, (const uint32_t*)tp[0].p, (uint32_t*)tp[1].p, (const int32_t*)tp[2].p, (int32_t*)tp[3].p, (int)n, 0, bits, st));
-    HCHK(hipcub::DeviceScan::ExclusiveSum(nullptr, scan_bytes, (const int64_t*)tp[5].p, (int64_t*)tp[6].p, (int)(n + 1), st));
-    if(tp[7].ensure(std::max(sort_bytes, scan_bytes) + 256)) return ald_set_err(ALD_ERR_NOMEM, "owner split scratch");
-    hipLaunchKernelGGL(tp_owner<REC>, dim3(grid_for(n)), dim3(TX_BLOCK), 0, st, s, skip_single, (uint32_t)world, (uint32_t*)tp[0].p, (int32_t*)tp[2].p, (int32_t*)tp[4].p);
-    HCHK(hipcub::DeviceRadixSort::SortPairs(tp[7].p, sort_bytes, (const uint32_t*)tp[0].p, (uint32_t*)tp[1].p, (const int32_t*)tp[2].p, (int32_t*)tp[3].p, (int)n, 0, bits, st));
-    hipLaunchKernelGGL(tp_gather, dim3(grid_for(n + 1)), dim3(TX_BLOCK), 0, st, (const int32_t*)tp[3].p, (const int32_t*)tp[4].p, n, (int64_t*)tp[5].p);
-    HCHK(hipcub::DeviceScan::ExclusiveSum(tp[7].p, scan_bytes, (const int64_t*)tp[5].p, (int64_t*)tp[6].p, (int)(n + 1), st));
-    hipLaunchKernelGGL(tp_bounds, dim3(grid_for(n + 1)), dim3(TX_BLOCK), 0, st, (const uint32_t*)tp[1].p, (const int64_t*)tp[6].p, n, world, (int64_t*)tp[8].p);
-    HCHK(hipMemcpyAsync(h_offsets, tp[8].p, 8 * (size_t)(world + 1), hipMemcpyDeviceToHost, st));
+    hipLaunchKernelGGL(tp_owner<REC>, dim3(grid_for(n)), dim3(TX_BLOCK), 0, st, s, skip_single, (uint32_t)world, (uint32_t*)T.owner.p, (int32_t*)T.ord.p, (int32_t*)T.len.p);
+    { int rc = tx_cub(T.cub_tmp, "owner split scratch", [&](void *t, size_t &nb) { return hipcub::DeviceRadixSort::SortPairs(t, nb, (const uint32_t*)T.owner.p, (uint32_t*)T.owner_sorted.p, (const int32_t*)T.ord.p, (int32_t*)T.ord_sorted.p, (int)n, 0, bits, st); }); if(rc != ALD_OK) return rc; }
+    hipLaunchKernelGGL(tp_gather, dim3(grid_for(n + 1)), dim3(TX_BLOCK), 0, st, (const int32_t*)T.ord_sorted.p, (const int32_t*)T.len.p, n, (int64_t*)T.len_sorted.p);
+    { int rc = tx_cub(T.cub_tmp, "owner split scratch", [&](void *t, size_t &nb) { return hipcub::DeviceScan::ExclusiveSum(t, nb, (const int64_t*)T.len_sorted.p, (int64_t*)T.place.p, (int)(n + 1), st); }); if(rc != ALD_OK) return rc; }
+    hipLaunchKernelGGL(tp_bounds, dim3(grid_for(n + 1)), dim3(TX_BLOCK), 0, st, (const uint32_t*)T.owner_sorted.p, (const int64_t*)T.place.p, n, world, (int64_t*)T.offsets.p);
+    HCHK(hipMemcpyAsync(h_offsets, T.offsets.p, 8 * (size_t)(world + 1), hipMemcpyDeviceToHost, st));
     HCHK(hipStreamSynchronize(st));
     if(hipGetLastError() != hipSuccess) return ald_set_err(ALD_ERR_HIP, "an owner-split kernel failed to launch");
     return ALD_OK;
 }
-template<bool REC> int tp_fill(hipStream_t st, DevBuf *tp, TpSrc s, const int32_t *d_sid, uint32_t *d_out)
+template<bool REC> int tp_fill(hipStream_t st, OwnerSplitScratch &T, TpSrc s, const int32_t *d_sid, uint32_t *d_out)
 {
-    hipLaunchKernelGGL(tp_emit<REC>, dim3(grid_for(16 * s.n)), dim3(TX_BLOCK), 0, st, s, (const int32_t*)tp[3].p, (const int64_t*)tp[6].p, d_sid, d_out);
+    hipLaunchKernelGGL(tp_emit<REC>, dim3(grid_for(16 * s.n)), dim3(TX_BLOCK), 0, st, s, (const int32_t*)T.ord_sorted.p, (const int64_t*)T.place.p, d_sid, d_out);
     HCHK(hipStreamSynchronize(st));
     if(hipGetLastError() != hipSuccess) return ald_set_err(ALD_ERR_HIP, "an owner-split kernel failed to launch");
     return ALD_OK;
@@ -125,7 +118,7 @@ int ald_batch_device_transcript_streams_by_owner(const ald_batch *cb, const int3
     *dev_words = nullptr; *offsets = b->tp_offsets.data();
     if(np == 0) return ALD_OK;
     { int rc = device_path_table(b); if(rc != ALD_OK) return rc; }
-    DevBuf &d_sid = b->red[10], &d_out = b->tp[TP_BUFS];
+    DevBuf &d_sid = b->tx.sid, &d_out = b->tp.out;
     hipStream_t st = b->stream;
     if(sid) { if(d_sid.ensure(4 * (size_t)n + 4)) return ald_set_err(ALD_ERR_NOMEM, "transcript stream buffers"); HCHK(hipMemcpyAsync(d_sid.p, sid, 4 * (size_t)n, hipMemcpyHostToDevice, st)); }
     TpSrc s; s.base = (const uint32_t*)b->d_pool.p; s.off = (const unsigned long long*)b->d_ordoff.p; s.n = np;
@@ -141,24 +134,22 @@ int ald_tset_split_stream(int32_t device, const uint32_t *words, int64_t n_words
 {
     if(!offsets || n_words < 0 || (n_words > 0 && (!words || !out_words))) return ALD_ERR_INVALID;
     if(world < 1 || world > 64) return ald_set_err(ALD_ERR_INVALID, "owner split: world must be in 1..64");
-    int ndev = 0;
-    if(hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return ald_set_err(ALD_ERR_NO_DEVICE, "no HIP device visible: the owner split has no CPU fallback");
-    if(device < 0 || device >= ndev) return ald_set_err(ALD_ERR_INVALID, "device index out of range");
+    { int rc = tx_need_device(device, "the owner split"); if(rc != ALD_OK) return rc; }
     HCHK(hipSetDevice(device));
     for(int r = 0; r <= world; r++) offsets[r] = 0;
     if(n_words == 0) return ALD_OK;
     const bool src_dev = tx_on_device(words), dst_dev = tx_on_device(out_words);
-    DevBuf tp[TP_BUFS], ix[IX_BUFS], d_in, d_off, d_out; PinBuf pin;
-    struct Rel { DevBuf *t, *x, *a, *b, *c; PinBuf *p; ~Rel() { for(int i = 0; i < TP_BUFS; i++) t[i].release(); for(int i = 0; i < IX_BUFS; i++) x[i].release(); a->release(); b->release(); c->release(); p->release(); } } rel{tp, ix, &d_in, &d_off, &d_out, &pin};
-    hipStream_t st = nullptr; HCHK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-    struct StRel { hipStream_t s; ~StRel() { hipStreamDestroy(s); } } strel{st};
+    Scoped<OwnerSplitScratch> tp; Scoped<StreamIndexScratch> ix; Scoped<DevBuf> d_in, d_off;
+    DevBuf &d_out = tp.out;                                 // (only when the caller's buffer is on the host)
+    ScopedStream stream; HCHK(hipStreamCreateWithFlags(&stream.s, hipStreamNonBlocking));
+    hipStream_t st = stream.s;
     if((!src_dev && d_in.ensure(4 * (size_t)n_words)) || (!dst_dev && d_out.ensure(4 * (size_t)n_words))) return ald_set_err(ALD_ERR_NOMEM, "owner split buffers");
     TpSrc s; s.base = src_dev ? words : (const uint32_t*)d_in.p;
     if(n_words < (int64_t)1 << 31) {
         // the transcript boundaries come from the stream index: a device stream stays where it is, a host stream is uploaded once
         if(!src_dev) HCHK(hipMemcpyAsync(d_in.p, words, 4 * (size_t)n_words, hipMemcpyHostToDevice, st));
         StreamIndex I;
-        { int rc = tx_stream_index(st, ix, pin, nullptr, nullptr, s.base, n_words, 0, I); if(rc != ALD_OK) return rc; }
+        { int rc = tx_stream_index(st, ix, nullptr, nullptr, s.base, n_words, 0, I); if(rc != ALD_OK) return rc; }
         s.off = I.toff; s.n = I.nt;
     } else {
         // 2^31 words or more, beyond the index's 32-bit nodes: the record walk on the host (as tx_stream_records walks); a device stream comes over for it
@@ -166,15 +157,7 @@ int ald_tset_split_stream(int32_t device, const uint32_t *words, int64_t n_words
         const uint32_t *h_words = words;
         if(src_dev) { staged.resize((size_t)n_words); HCHK(hipMemcpy(staged.data(), words, 4 * (size_t)n_words, hipMemcpyDeviceToHost)); h_words = staged.data(); }
         std::vector<unsigned long long> toff;
-        { int64_t last = -1;
-          for(int64_t o = 0; o < n_words; ) {
-              if(o + ALD_TS_HDR > n_words) return ald_set_err(ALD_ERR_INVALID, "malformed transcript stream");
-              const int64_t len = ALD_TS_HDR + 2 * (int64_t)h_words[o + 5];
-              if((int32_t)h_words[o + 5] < 0 || o + len > n_words) return ald_set_err(ALD_ERR_INVALID, "malformed transcript stream");
-              const int64_t g = (int64_t)h_words[o];
-              if(g < last) return ald_set_err(ALD_ERR_INVALID, "transcript stream not in ascending graph order");
-              last = g; toff.push_back((unsigned long long)o); o += len;
-          } }
+        { int rc = tx_walk_stream(h_words, n_words, [&](int64_t o, bool) { toff.push_back((unsigned long long)o); }); if(rc != ALD_OK) return rc; }
         const int64_t nt = (int64_t)toff.size();
         if(d_off.ensure(8 * (size_t)nt)) return ald_set_err(ALD_ERR_NOMEM, "owner split buffers");
         if(!src_dev) HCHK(hipMemcpyAsync(d_in.p, words, 4 * (size_t)n_words, hipMemcpyHostToDevice, st));

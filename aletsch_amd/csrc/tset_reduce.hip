@@ -201,14 +201,11 @@ int device_path_table(ald_batch *b)
     if(b->paths_on_device) return ALD_OK;
     const int n = b->hb.n(); const int64_t np = b->total_paths;
     if(n == 0 || np == 0) { b->paths_on_device = true; return ALD_OK; }
-    DevBuf &d_len = b->dts[0], &d_tmp = b->red[14];
+    DevBuf &d_len = b->d_ts_len;
     if(b->d_pbegin.ensure(8 * (size_t)n + 8) || b->d_ordoff.ensure(8 * (size_t)np + 8) || d_len.ensure(8 * (size_t)n + 8)) return ald_set_err(ALD_ERR_NOMEM, "device path table");
     hipStream_t st = b->stream;
     hipLaunchKernelGGL(ix_widen, dim3(grid_for(n + 1)), dim3(TX_BLOCK), 0, st, (const int32_t*)b->d_npaths.p, n, (int64_t*)d_len.p);
-    size_t scan_bytes = 0;
-    HCHK(hipcub::DeviceScan::ExclusiveSum(nullptr, scan_bytes, (const int64_t*)d_len.p, (int64_t*)b->d_pbegin.p, n + 1, st));
-    if(d_tmp.ensure(scan_bytes + 256)) return ald_set_err(ALD_ERR_NOMEM, "scan scratch");
-    HCHK(hipcub::DeviceScan::ExclusiveSum(d_tmp.p, scan_bytes, (const int64_t*)d_len.p, (int64_t*)b->d_pbegin.p, n + 1, st));
+    { int rc = tx_cub(b->tx.cub_tmp, "scan scratch", [&](void *t, size_t &nb) { return hipcub::DeviceScan::ExclusiveSum(t, nb, (const int64_t*)d_len.p, (int64_t*)b->d_pbegin.p, n + 1, st); }); if(rc != ALD_OK) return rc; }
     hipLaunchKernelGGL(ix_order, dim3(grid_for(n)), dim3(TX_BLOCK), 0, st, (const int32_t*)b->d_npaths.p, (const int64_t*)b->d_pbegin.p, (const long long*)b->d_gfirst.p, (const unsigned long long*)b->d_index.p, n, (unsigned long long*)b->d_ordoff.p);
     if(hipGetLastError() != hipSuccess) return ald_set_err(ALD_ERR_HIP, "a path-table kernel failed to launch");
     b->paths_on_device = true;
@@ -220,9 +217,10 @@ int tx_front_sort(RedScratch S, TxIn in, const double *h_cov, int n_graphs, cons
     const int64_t np = in.np;
     F.np = np; F.n_dev = 0; F.n_groups = 0; F.n_runs = 0; F.host_paths.clear(); F.sid_on_device = sid != nullptr; F.h_cov = nullptr;
     if(np == 0) { if(F.ev0) HCHK(hipEventRecord(F.ev0, S.st)); return ALD_OK; }
-    DevBuf &d_cov = S.red[2], &d_w = S.red[3], &d_nw = S.red[4], &d_key = S.red[5], &d_key2 = S.red[6], &d_idx = S.red[7], &d_idx2 = S.red[8], &d_graph = S.red[9],
-           &d_sid = S.red[10], &d_head = S.red[11], &d_gid = S.red[12], &d_tmp = S.red[14], &d_head2 = S.red[15], &d_rid = S.red[16], &d_pos = S.red[18], &d_pos2 = S.red[19];
-    PinBuf &p_key = S.pin[0], &p_w = S.pin[4], &p_cov = S.pin[5];
+    TxScratch &X = *S.x;
+    DevBuf &d_cov = X.cov, &d_w = X.weight, &d_nw = X.nw, &d_key = X.key, &d_key2 = X.key_sorted, &d_idx = X.idx, &d_idx2 = X.sidx, &d_graph = X.graph,
+           &d_sid = X.sid, &d_head = X.head, &d_gid = X.gid, &d_head2 = X.run_head, &d_rid = X.run_id, &d_pos = X.pos, &d_pos2 = X.pos_sorted;
+    PinBuf &p_key = X.p_key, &p_w = X.p_weight, &p_cov = X.p_cov;
     const bool from_records = h_cov == nullptr && F.d_cov == nullptr;
     if(from_records && !F.ev_w) return ald_set_err(ALD_ERR_INVALID, "tx_front_sort: coverage from the records needs an event");
     if(p_key.ensure(8 * (size_t)np, true) || (from_records && (p_w.ensure(8 * (size_t)np, true) || p_cov.ensure(8 * (size_t)np)))) return ald_set_err(ALD_ERR_NOMEM, "pinned reduction buffers");
@@ -241,12 +239,7 @@ int tx_front_sort(RedScratch S, TxIn in, const double *h_cov, int n_graphs, cons
     } else hipLaunchKernelGGL(tx_build<false>, dim3(grid_for(np)), dim3(TX_BLOCK), 0, st, in, (int32_t*)d_nw.p, (uint64_t*)d_key.p, (int32_t*)d_graph.p, (double*)nullptr);
     hipLaunchKernelGGL(tx_iota, dim3(grid_for(np)), dim3(TX_BLOCK), 0, st, (int64_t*)d_idx.p, np);
     // stable sort by group key: members of a group stay in (graph, path) order; host-side transcripts (key = ~0) sink to the end
-    size_t tmp_bytes = 0;
-    HCHK(hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_bytes, (const uint64_t*)d_key.p, (uint64_t*)d_key2.p, (const int64_t*)d_idx.p, (int64_t*)d_idx2.p, (int)np, 0, 64, st));
-    size_t scan_bytes = 0;
-    HCHK(hipcub::DeviceScan::InclusiveSum(nullptr, scan_bytes, (const int32_t*)d_head.p, (int32_t*)d_gid.p, (int)np, st));
-    if(d_tmp.ensure(std::max(tmp_bytes, scan_bytes) + 256)) return ald_set_err(ALD_ERR_NOMEM, "sort scratch");
-    HCHK(hipcub::DeviceRadixSort::SortPairs(d_tmp.p, tmp_bytes, (const uint64_t*)d_key.p, (uint64_t*)d_key2.p, (const int64_t*)d_idx.p, (int64_t*)d_idx2.p, (int)np, 0, 64, st));
+    { int rc = tx_cub(X.cub_tmp, "sort scratch", [&](void *t, size_t &nb) { return hipcub::DeviceRadixSort::SortPairs(t, nb, (const uint64_t*)d_key.p, (uint64_t*)d_key2.p, (const int64_t*)d_idx.p, (int64_t*)d_idx2.p, (int)np, 0, 64, st); }); if(rc != ALD_OK) return rc; }
     // how many went to the device: the sorted keys below TX_HOST (tx_front_heads looks)
     HCHK(hipMemcpyAsync(p_key.p, d_key2.p, 8 * (size_t)np, hipMemcpyDeviceToHost, st)); tx_count_d2h(S, 8 * (size_t)np);
     return ALD_OK;
@@ -257,10 +250,10 @@ int tx_front_coverage(RedScratch S, TxFront &F)
     const int64_t np = F.np;
     if(np == 0) return ALD_OK;
     HCHK(hipEventSynchronize(F.ev_w));                     // the weights are in pinned memory; the sort is running
-    const double *w = (const double*)S.pin[4].p; double *cov = (double*)S.pin[5].p;
+    const double *w = (const double*)S.x->p_weight.p; double *cov = (double*)S.x->p_cov.p;
     const unsigned nthr = ald_sink_threads(np);
     HostBatch::run_threads(nthr, [&](unsigned th) { for(int64_t i = np * th / nthr; i < np * (th + 1) / nthr; i++) cov[(size_t)i] = log(1.0 + w[(size_t)i]); });      // essential.cc:725, host libm
-    HCHK(hipMemcpyAsync(S.red[2].p, cov, 8 * (size_t)np, hipMemcpyHostToDevice, S.st));
+    HCHK(hipMemcpyAsync(S.x->cov.p, cov, 8 * (size_t)np, hipMemcpyHostToDevice, S.st));
     F.h_cov = cov;
     return ALD_OK;
 }
@@ -269,17 +262,15 @@ int tx_front_heads(RedScratch S, TxIn in, TxFront &F)
 {
     const int64_t np = F.np;
     if(np == 0) return ALD_OK;
-    DevBuf &d_key2 = S.red[6], &d_idx2 = S.red[8], &d_head = S.red[11], &d_gid = S.red[12], &d_tmp = S.red[14];
+    DevBuf &d_key2 = S.x->key_sorted, &d_idx2 = S.x->sidx, &d_head = S.x->head, &d_gid = S.x->gid;
     hipStream_t st = S.st;
-    const uint64_t *h_key = (const uint64_t*)S.pin[0].p;
+    const uint64_t *h_key = (const uint64_t*)S.x->p_key.p;
     HCHK(hipStreamSynchronize(st));
     const int64_t n_dev = (int64_t)(std::lower_bound(h_key, h_key + np, TX_HOST) - h_key);
     F.n_dev = n_dev;
     if(n_dev > 0) {
-        size_t scan_bytes = 0;
-        HCHK(hipcub::DeviceScan::InclusiveSum(nullptr, scan_bytes, (const int32_t*)d_head.p, (int32_t*)d_gid.p, (int)np, st));      // (d_tmp holds at least this: tx_front_sort)
         hipLaunchKernelGGL(tx_heads, dim3(grid_for(n_dev)), dim3(TX_BLOCK), 0, st, in, (const uint64_t*)d_key2.p, (const int64_t*)d_idx2.p, n_dev, (int32_t*)d_head.p);
-        HCHK(hipcub::DeviceScan::InclusiveSum(d_tmp.p, scan_bytes, (const int32_t*)d_head.p, (int32_t*)d_gid.p, (int)n_dev, st));
+        { int rc = tx_cub(S.x->cub_tmp, "scan scratch", [&](void *t, size_t &nb) { return hipcub::DeviceScan::InclusiveSum(t, nb, (const int32_t*)d_head.p, (int32_t*)d_gid.p, (int)n_dev, st); }); if(rc != ALD_OK) return rc; }
         HCHK(hipMemcpyAsync(&F.n_groups, (int32_t*)d_gid.p + (n_dev - 1), 4, hipMemcpyDeviceToHost, st)); tx_count_d2h(S, 4);
     }
     // the transcripts left to the host: the tail of the sorted order (key TX_HOST; the stable sort kept them in (graph, path) order)
@@ -302,16 +293,13 @@ int tx_compact_singles(RedScratch S, TxIn in, const TxFront &F, DevBuf &d_out, c
     const int64_t ns = (int64_t)F.host_paths.size();
     *h_words = nullptr; *h_off = nullptr;
     if(ns == 0) return ALD_OK;
-    DevBuf &d_len = S.red[0], &d_at = S.red[1], &d_tmp = S.red[14];
-    PinBuf &p_off = S.pin[6], &p_words = S.pin[7];
+    DevBuf &d_len = S.x->single_len, &d_at = S.x->single_at;
+    PinBuf &p_off = S.x->p_single_off, &p_words = S.x->p_single_words;
     hipStream_t st = S.st;
     const int64_t *hp = tx_sidx(S) + F.n_dev;             // the tail of the sorted order, still on the device
     if(d_len.ensure(8 * (size_t)(ns + 1)) || d_at.ensure(8 * (size_t)(ns + 1)) || p_off.ensure(8 * (size_t)(ns + 1), true)) return ald_set_err(ALD_ERR_NOMEM, "single-exon compaction");
     hipLaunchKernelGGL(sx_len, dim3(grid_for(ns + 1)), dim3(TX_BLOCK), 0, st, in, hp, ns, (int64_t*)d_len.p);
-    size_t scan_bytes = 0;
-    HCHK(hipcub::DeviceScan::ExclusiveSum(nullptr, scan_bytes, (const int64_t*)d_len.p, (int64_t*)d_at.p, (int)(ns + 1), st));
-    if(d_tmp.ensure(scan_bytes + 256)) return ald_set_err(ALD_ERR_NOMEM, "scan scratch");
-    HCHK(hipcub::DeviceScan::ExclusiveSum(d_tmp.p, scan_bytes, (const int64_t*)d_len.p, (int64_t*)d_at.p, (int)(ns + 1), st));
+    { int rc = tx_cub(S.x->cub_tmp, "scan scratch", [&](void *t, size_t &nb) { return hipcub::DeviceScan::ExclusiveSum(t, nb, (const int64_t*)d_len.p, (int64_t*)d_at.p, (int)(ns + 1), st); }); if(rc != ALD_OK) return rc; }
     HCHK(hipMemcpyAsync(p_off.p, d_at.p, 8 * (size_t)(ns + 1), hipMemcpyDeviceToHost, st)); tx_count_d2h(S, 8 * (size_t)(ns + 1));
     HCHK(hipStreamSynchronize(st));
     const int64_t total = ((const int64_t*)p_off.p)[ns];
@@ -327,26 +315,23 @@ int tx_front_fold(RedScratch S, TxIn in, TxFront &F, const int64_t *start_idx, c
 {
     const int64_t n_dev = F.n_dev; F.n_runs = 0;
     if(n_dev == 0) return ALD_OK;
-    DevBuf &d_cov = S.red[2], &d_key = S.red[5], &d_idx = S.red[7], &d_graph = S.red[9], &d_sid = S.red[10], &d_groups = S.red[13], &d_tmp = S.red[14],
-           &d_head2 = S.red[15], &d_rid = S.red[16], &d_samples = S.red[17], &d_pos = S.red[18], &d_pos2 = S.red[19];
+    TxScratch &X = *S.x;
+    DevBuf &d_cov = X.cov, &d_graph = X.graph, &d_sid = X.sid, &d_groups = X.groups, &d_head2 = X.run_head, &d_rid = X.run_id, &d_samples = X.samples, &d_pos = X.pos, &d_pos2 = X.pos_sorted;
+    DevBuf &d_skey = X.key, &d_skey2 = X.idx;                // second lives: both are free once the first sort is done and its keys are in key_sorted
     hipStream_t st = S.st;
     const uint64_t *skey = tx_skey(S); const int64_t *sidx = tx_sidx(S);
     if(d_groups.ensure(sizeof(TxGroup) * (size_t)F.n_groups)) return ald_set_err(ALD_ERR_NOMEM, "group records");
     hipLaunchKernelGGL(tx_fold, dim3(grid_for(n_dev)), dim3(TX_BLOCK), 0, st, in, skey, sidx, tx_head(S), tx_gid(S), n_dev, (const double*)d_cov.p, start_idx, start_cov, (TxGroup*)d_groups.p);
     // per-sample copies: second stable sort by (group, sample)
-    hipLaunchKernelGGL(tx_skeys, dim3(grid_for(n_dev)), dim3(TX_BLOCK), 0, st, sidx, tx_gid(S), (const int32_t*)d_graph.p, F.sid_on_device ? (const int32_t*)d_sid.p : (const int32_t*)nullptr, n_dev, (uint64_t*)d_key.p);
+    hipLaunchKernelGGL(tx_skeys, dim3(grid_for(n_dev)), dim3(TX_BLOCK), 0, st, sidx, tx_gid(S), (const int32_t*)d_graph.p, F.sid_on_device ? (const int32_t*)d_sid.p : (const int32_t*)nullptr, n_dev, (uint64_t*)d_skey.p);
     hipLaunchKernelGGL(tx_iota, dim3(grid_for(n_dev)), dim3(TX_BLOCK), 0, st, (int64_t*)d_pos.p, n_dev);
-    size_t tmp_bytes = 0, scan_bytes = 0;
-    HCHK(hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_bytes, (const uint64_t*)d_key.p, (uint64_t*)d_idx.p, (const int64_t*)d_pos.p, (int64_t*)d_pos2.p, (int)n_dev, 0, 64, st));
-    HCHK(hipcub::DeviceScan::InclusiveSum(nullptr, scan_bytes, (const int32_t*)d_head2.p, (int32_t*)d_rid.p, (int)n_dev, st));
-    if(d_tmp.ensure(std::max(tmp_bytes, scan_bytes) + 256)) return ald_set_err(ALD_ERR_NOMEM, "sort scratch");
-    HCHK(hipcub::DeviceRadixSort::SortPairs(d_tmp.p, tmp_bytes, (const uint64_t*)d_key.p, (uint64_t*)d_idx.p /* sorted key2 */, (const int64_t*)d_pos.p, (int64_t*)d_pos2.p, (int)n_dev, 0, 64, st));
-    hipLaunchKernelGGL(tx_sheads, dim3(grid_for(n_dev)), dim3(TX_BLOCK), 0, st, (const uint64_t*)d_idx.p, n_dev, (int32_t*)d_head2.p);
-    HCHK(hipcub::DeviceScan::InclusiveSum(d_tmp.p, scan_bytes, (const int32_t*)d_head2.p, (int32_t*)d_rid.p, (int)n_dev, st));
+    { int rc = tx_cub(X.cub_tmp, "sort scratch", [&](void *t, size_t &nb) { return hipcub::DeviceRadixSort::SortPairs(t, nb, (const uint64_t*)d_skey.p, (uint64_t*)d_skey2.p, (const int64_t*)d_pos.p, (int64_t*)d_pos2.p, (int)n_dev, 0, 64, st); }); if(rc != ALD_OK) return rc; }
+    hipLaunchKernelGGL(tx_sheads, dim3(grid_for(n_dev)), dim3(TX_BLOCK), 0, st, (const uint64_t*)d_skey2.p, n_dev, (int32_t*)d_head2.p);
+    { int rc = tx_cub(X.cub_tmp, "scan scratch", [&](void *t, size_t &nb) { return hipcub::DeviceScan::InclusiveSum(t, nb, (const int32_t*)d_head2.p, (int32_t*)d_rid.p, (int)n_dev, st); }); if(rc != ALD_OK) return rc; }
     HCHK(hipMemcpyAsync(&F.n_runs, (int32_t*)d_rid.p + (n_dev - 1), 4, hipMemcpyDeviceToHost, st)); tx_count_d2h(S, 4);
     HCHK(hipStreamSynchronize(st));
     if(d_samples.ensure(sizeof(TxSample) * (size_t)F.n_runs)) return ald_set_err(ALD_ERR_NOMEM, "sample records");
-    hipLaunchKernelGGL(tx_sfold, dim3(grid_for(n_dev)), dim3(TX_BLOCK), 0, st, in, (const uint64_t*)d_idx.p, (const int64_t*)d_pos2.p, sidx, (const int32_t*)d_head2.p, (const int32_t*)d_rid.p, n_dev,
+    hipLaunchKernelGGL(tx_sfold, dim3(grid_for(n_dev)), dim3(TX_BLOCK), 0, st, in, (const uint64_t*)d_skey2.p, (const int64_t*)d_pos2.p, sidx, (const int32_t*)d_head2.p, (const int32_t*)d_rid.p, n_dev,
                        (const double*)d_cov.p, (TxSample*)d_samples.p);
     if(hipGetLastError() != hipSuccess) return ald_set_err(ALD_ERR_HIP, "a reduction kernel failed to launch");
     return ALD_OK;
@@ -384,16 +369,12 @@ void tx_host_singles(aletsch::transcript_sink &into, const std::vector<int64_t> 
 int tx_stream_records(const uint32_t *words, int64_t n_words, const double *coverage, const int64_t *tid, int32_t skip_single_exon, int64_t graph_offset, StreamRecords &R)
 {
     std::vector<uint32_t> &pool = R.pool; std::vector<unsigned long long> &roff = R.roff; std::vector<double> &cov = R.cov; std::vector<int32_t> &sid = R.sid; std::vector<int64_t> &label = R.label, &tids = R.tids;
-    int64_t last = -1, ti = -1;                            // ti: ordinal of the transcript in the stream (index into `coverage`)
-    for(int64_t o = 0; o < n_words; ) {
+    int64_t ti = -1;                                       // ti: ordinal of the transcript in the stream (index into `coverage`)
+    const int rc = tx_walk_stream(words, n_words, [&](int64_t o, bool first) {
         ti++;
-        if(o + ALD_TS_HDR > n_words) return ald_set_err(ALD_ERR_INVALID, "malformed transcript stream");
-        const int64_t k = 2 * (int64_t)words[o + 5], len = ALD_TS_HDR + k;
-        if((int32_t)words[o + 5] < 0 || o + len > n_words) return ald_set_err(ALD_ERR_INVALID, "malformed transcript stream");
-        const int64_t g = (int64_t)words[o];
-        if(g < last) return ald_set_err(ALD_ERR_INVALID, "transcript stream not in ascending graph order");
-        if(g != last) { label.push_back(g + graph_offset); sid.push_back((int32_t)words[o + 2]); last = g; }
-        if(skip_single_exon && k <= 2) { o += len; continue; }
+        const int64_t k = 2 * (int64_t)words[o + 5];
+        if(first) { label.push_back((int64_t)words[o] + graph_offset); sid.push_back((int32_t)words[o + 2]); }
+        if(skip_single_exon && k <= 2) return;
         const size_t at = pool.size(); roff.push_back((unsigned long long)at);
         pool.resize(at + (size_t)rec_words(2, (unsigned)k), 0);
         uint32_t *r = pool.data() + at;
@@ -401,15 +382,13 @@ int tx_stream_records(const uint32_t *words, int64_t n_words, const double *cove
         r[6] = words[o + 6]; r[7] = words[o + 7]; r[8] = words[o + 10]; r[9] = words[o + 11]; r[10] = words[o + 8]; r[11] = words[o + 9]; r[12] = r[13] = 0; r[REC_NEXW] = (uint32_t)k; r[REC_NEXW + 1] = 0;
         memcpy(r + REC_HDR_WORDS + 2, words + o + ALD_TS_HDR, 4 * (size_t)k);
         double w; memcpy(&w, words + o + 6, 8); cov.push_back(coverage ? coverage[ti] : log(1.0 + w)); if(tid) tids.push_back(tid[ti]);
-        o += len;
-    }
+    });
+    if(rc != ALD_OK) return rc;
     R.n_transcripts = ti + 1;
     return ALD_OK;
 }
 
 namespace {
-struct EventPair { hipEvent_t a = nullptr, b = nullptr; ~EventPair() { if(a) hipEventDestroy(a); if(b) hipEventDestroy(b); } };
-
 // The reduction proper.  d_pool / d_roff: record pool and record offsets in (graph, path) order in HBM; h_pool / h_roff: the same on
 // the host (pinned landing areas); h_cov: log(1 + weight) per path (host libm: these values are summed, and the sums are compared bit
 // for bit with the host sink); sid: sample of every graph or null; label: graph id that goes into the transcript ids (null: the
@@ -425,7 +404,7 @@ int reduce_core(RedScratch S, const uint32_t *d_pool, const unsigned long long *
     size_t NGd = 0, NSd = 0; TxFront X;
     const TxGroup *groups = nullptr; const TxSample *samples = nullptr;
     if(np > 0) {
-        PinBuf &p_groups = S.pin[1], &p_samples = S.pin[2];
+        PinBuf &p_groups = S.x->p_groups, &p_samples = S.x->p_samples;
         hipStream_t st = S.st;
         EventPair ev; HCHK(hipEventCreate(&ev.a)); HCHK(hipEventCreate(&ev.b));
         TxIn in; in.roff = d_roff; in.pool = d_pool; in.np = np;
@@ -528,7 +507,7 @@ int ald_batch_reduce_transcripts(const ald_batch *cb, const int32_t *sid, int64_
     // the host's side: the record pool is in the batch's pinned landing area, the offsets in (graph, path) order and the coverages
     // (log(1 + weight), host libm) are the path table ald_batch_download built from the kernel's index
     const unsigned long long *h_roff = (const unsigned long long*)b->res.rec_off.data(); const double *h_cov = b->res.coverage.data();
-    RedScratch S; S.red = b->red; S.pin = b->red_pin; S.st = b->stream;
+    RedScratch S; S.x = &b->tx; S.st = b->stream;
     return reduce_core(S, (const uint32_t*)b->d_pool.p, (const unsigned long long*)b->d_ordoff.p, b->res.pool_data(), h_roff, h_cov, nullptr, np, b->hb.n(), sid, nullptr, tid_base, skip_single_exon, single_exon_overlap, out);
 }
 
@@ -539,25 +518,22 @@ int ald_batch_reduce_transcripts(const ald_batch *cb, const int32_t *sid, int64_
 int ald_tset_reduce_stream(int32_t device, const uint32_t *words, int64_t n_words, const double *coverage, const int64_t *tid, int64_t tid_base, int32_t skip_single_exon, double single_exon_overlap, ald_tset_flat **out)
 {
     if(!out || n_words < 0 || (n_words > 0 && !words)) return ALD_ERR_INVALID;
-    int ndev = 0;
-    if(hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return ald_set_err(ALD_ERR_NO_DEVICE, "no HIP device visible: the reduction has no CPU fallback");
-    if(device < 0 || device >= ndev) return ald_set_err(ALD_ERR_INVALID, "device index out of range");
+    { int rc = tx_need_device(device, "the reduction"); if(rc != ALD_OK) return rc; }
     HCHK(hipSetDevice(device));
     StreamRecords R;
     { int rc = tx_stream_records(words, n_words, coverage, tid, skip_single_exon, 0, R); if(rc != ALD_OK) return rc; }
     std::vector<uint32_t> &pool = R.pool; std::vector<unsigned long long> &roff = R.roff; std::vector<double> &cov = R.cov; std::vector<int32_t> &sid = R.sid; std::vector<int64_t> &label = R.label, &tids = R.tids;
     const int64_t np = (int64_t)roff.size();
-    DevBuf red[20], d_pool, d_roff; PinBuf pin[8];
-    struct Rel { DevBuf *r, *a, *c; PinBuf *p; ~Rel() { for(int i = 0; i < 20; i++) r[i].release(); a->release(); c->release(); for(int i = 0; i < 8; i++) p[i].release(); } } rel{red, &d_pool, &d_roff, pin};
-    hipStream_t st = nullptr; HCHK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-    struct StRel { hipStream_t s; ~StRel() { hipStreamDestroy(s); } } strel{st};
+    Scoped<TxScratch> tx; Scoped<DevBuf> d_pool, d_roff;
+    ScopedStream stream; HCHK(hipStreamCreateWithFlags(&stream.s, hipStreamNonBlocking));
+    hipStream_t st = stream.s;
     if(np > 0) {
         if(d_pool.ensure(4 * pool.size() + 64) || d_roff.ensure(8 * (size_t)np + 8)) return ald_set_err(ALD_ERR_NOMEM, "stream reduction buffers");
         HCHK(hipMemcpyAsync(d_pool.p, pool.data(), 4 * pool.size(), hipMemcpyHostToDevice, st));
         HCHK(hipMemcpyAsync(d_roff.p, roff.data(), 8 * (size_t)np, hipMemcpyHostToDevice, st));
         HCHK(hipStreamSynchronize(st));
     }
-    RedScratch S; S.red = red; S.pin = pin; S.st = st;
+    RedScratch S; S.x = &tx; S.st = st;
     return reduce_core(S, (const uint32_t*)d_pool.p, (const unsigned long long*)d_roff.p, pool.data(), roff.data(), cov.data(), tid ? tids.data() : nullptr, np, (int)label.size(), sid.empty() ? nullptr : sid.data(), label.data(), tid_base, 0 /* filtered above */, single_exon_overlap, out);
 }
 
@@ -575,19 +551,16 @@ int ald_batch_device_transcript_stream(const ald_batch *cb, const int32_t *sid, 
     *dev_words = nullptr; *n_words = 0;
     if(np == 0) return ALD_OK;
     { int rc = device_path_table(b); if(rc != ALD_OK) return rc; }
-    PinBuf &p_tot = b->red_pin[7];
-    DevBuf &d_sid = b->red[10], &d_tmp = b->red[14];
-    DevBuf &d_len = b->dts[0], &d_at = b->dts[1], &d_out = b->dts[2];
+    PinBuf &p_tot = b->tx.p_count;
+    DevBuf &d_sid = b->tx.sid;
+    DevBuf &d_len = b->d_ts_len, &d_at = b->d_ts_at, &d_out = b->d_ts_out;
     if(p_tot.ensure(64)) return ald_set_err(ALD_ERR_NOMEM, "pinned counter");
     if(d_len.ensure(8 * (size_t)std::max<int64_t>(np, n) + 8) || d_at.ensure(8 * (size_t)np + 8) || (sid && d_sid.ensure(4 * (size_t)n + 4))) return ald_set_err(ALD_ERR_NOMEM, "transcript stream buffers");
     hipStream_t st = b->stream;
     if(sid) HCHK(hipMemcpyAsync(d_sid.p, sid, 4 * (size_t)n, hipMemcpyHostToDevice, st));
     TxIn in; in.roff = (const unsigned long long*)b->d_ordoff.p; in.pool = (const uint32_t*)b->d_pool.p; in.np = np;
     hipLaunchKernelGGL(ts_len, dim3(grid_for(np + 1)), dim3(TX_BLOCK), 0, st, in, (int)(skip_single_exon != 0), (int64_t*)d_len.p);
-    size_t scan_bytes = 0;
-    HCHK(hipcub::DeviceScan::ExclusiveSum(nullptr, scan_bytes, (const int64_t*)d_len.p, (int64_t*)d_at.p, (int)(np + 1), st));
-    if(d_tmp.ensure(scan_bytes + 256)) return ald_set_err(ALD_ERR_NOMEM, "scan scratch");
-    HCHK(hipcub::DeviceScan::ExclusiveSum(d_tmp.p, scan_bytes, (const int64_t*)d_len.p, (int64_t*)d_at.p, (int)(np + 1), st));
+    { int rc = tx_cub(b->tx.cub_tmp, "scan scratch", [&](void *t, size_t &nb) { return hipcub::DeviceScan::ExclusiveSum(t, nb, (const int64_t*)d_len.p, (int64_t*)d_at.p, (int)(np + 1), st); }); if(rc != ALD_OK) return rc; }
     HCHK(hipMemcpyAsync(p_tot.p, (const int64_t*)d_at.p + np, 8, hipMemcpyDeviceToHost, st));
     HCHK(hipStreamSynchronize(st));
     const int64_t total = *(const int64_t*)p_tot.p;

@@ -307,9 +307,9 @@ struct ald_tset_dev {
     hipEvent_t ev_w = nullptr;                              // behind the D2H of a finished batch's weights (tx_front_sort)
     SetBufs buf[2]; int cur = 0;
     aletsch::transcript_sink single;                        // transcripts with fewer than two exons, in call order
-    DevBuf red[20], d_pool, d_roff, d_label, d_tid; PinBuf pin[8];          // front end scratch (the set's own, never a batch's)
-    DevBuf w[16];                                           // merge-path scratch ([14]: the compacted single-exon records of a finished batch)
-    DevBuf ix[IX_BUFS], sr[9]; PinBuf pin_ix, pin_sr;       // a device stream: the stream index, the record build (sr_len / sr_emit)
+    TxScratch tx; DevBuf d_pool, d_roff, d_label, d_tid;    // front end scratch (the set's own, never a batch's)
+    MergeScratch mg;                                        // merge-path scratch
+    StreamIndexScratch ix; StreamRecScratch sr;             // a device stream: the stream index, the record build (sr_len / sr_emit)
     hipEvent_t ev_i0 = nullptr, ev_i1 = nullptr;            // around the index kernels
     double last_device_ms = 0, last_call_ms = 0;
     // of the last ald_tset_dev_add_stream (ald_tset_dev_stream_stats)
@@ -319,8 +319,7 @@ struct ald_tset_dev {
     const SetBufs &res() const { return buf[cur]; }
     ~ald_tset_dev() {
         for(auto &b : buf) b.release();
-        for(auto &d : red) d.release(); for(auto &d : w) d.release(); for(auto &p : pin) p.release();
-        for(auto &d : ix) d.release(); for(auto &d : sr) d.release(); pin_ix.release(); pin_sr.release();
+        tx.release(); mg.release(); ix.release(); sr.release();
         if(ev_i0) hipEventDestroy(ev_i0); if(ev_i1) hipEventDestroy(ev_i1);
         d_pool.release(); d_roff.release(); d_label.release(); d_tid.release();
         if(ev0) hipEventDestroy(ev0); if(ev1) hipEventDestroy(ev1); if(ev_w) hipEventDestroy(ev_w);
@@ -337,18 +336,16 @@ template<class In> int merge_path(ald_tset_dev *s, In B, const int64_t *match, c
     hipStream_t st = s->st;
     SetBufs &Ab = s->res(), &Ob = s->buf[s->cur ^ 1];
     const SetView A = Ab.view(); const int64_t nA = Ab.n, nB = B.n;
-    DevBuf &d_ub = s->w[6], &d_cnt = s->w[7], &d_shift = s->w[8], &d_rmatch = s->w[9], &d_slot = s->w[10], &d_ecnt = s->w[11], &d_scnt = s->w[12], &d_tmp = s->w[15];
+    MergeScratch &M = s->mg;
+    DevBuf &d_ub = M.ub, &d_cnt = M.cnt, &d_shift = M.shift, &d_rmatch = M.rmatch, &d_slot = M.slot, &d_ecnt = M.ecnt, &d_scnt = M.scnt, &d_tmp = M.cub_tmp;
     if(d_ub.ensure(4 * (size_t)(nB + 1)) || d_cnt.ensure(4 * (size_t)(nA + 1)) || d_shift.ensure(4 * (size_t)(nA + 1)) || d_rmatch.ensure(8 * (size_t)(nA + 1))) return ald_set_err(ALD_ERR_NOMEM, "resident set merge scratch");
-    size_t t1 = 0, t2 = 0;
-    HCHK(hipcub::DeviceScan::ExclusiveSum(nullptr, t1, (const int32_t*)unm, (int32_t*)d_ub.p, (int)(nB + 1), st));
-    HCHK(hipcub::DeviceScan::InclusiveSum(nullptr, t2, (const int32_t*)d_cnt.p, (int32_t*)d_shift.p, (int)(nA + 1), st));
-    if(d_tmp.ensure(std::max(t1, t2) + 256)) return ald_set_err(ALD_ERR_NOMEM, "resident set scan scratch");
-    HCHK(hipcub::DeviceScan::ExclusiveSum(d_tmp.p, t1, (const int32_t*)unm, (int32_t*)d_ub.p, (int)(nB + 1), st));
+    const char *const scan = "resident set scan scratch";
+    { int rc = tx_cub(d_tmp, scan, [&](void *t, size_t &nb) { return hipcub::DeviceScan::ExclusiveSum(t, nb, (const int32_t*)unm, (int32_t*)d_ub.p, (int)(nB + 1), st); }); if(rc != ALD_OK) return rc; }
     HCHK(hipMemsetAsync(d_cnt.p, 0, 4 * (size_t)(nA + 1), st));
     HCHK(hipMemsetAsync(d_rmatch.p, 0xFF, 8 * (size_t)(nA + 1), st));
     if(nB > 0) hipLaunchKernelGGL(rs_mark, dim3(grid_for(nB)), dim3(TX_BLOCK), 0, st, match, ins, nB, (int64_t*)d_rmatch.p, (int32_t*)d_cnt.p);
-    HCHK(hipcub::DeviceScan::InclusiveSum(d_tmp.p, t2, (const int32_t*)d_cnt.p, (int32_t*)d_shift.p, (int)(nA + 1), st));
-    PinBuf &p_cnt = s->pin[3];
+    { int rc = tx_cub(d_tmp, scan, [&](void *t, size_t &nb) { return hipcub::DeviceScan::InclusiveSum(t, nb, (const int32_t*)d_cnt.p, (int32_t*)d_shift.p, (int)(nA + 1), st); }); if(rc != ALD_OK) return rc; }
+    PinBuf &p_cnt = s->tx.p_count;
     if(p_cnt.ensure(64)) return ald_set_err(ALD_ERR_NOMEM, "pinned counter");
     int64_t *hc = (int64_t*)p_cnt.p;
     { int32_t *u = (int32_t*)(hc + 4); HCHK(hipMemcpyAsync(u, (const int32_t*)d_ub.p + nB, 4, hipMemcpyDeviceToHost, st)); HCHK(hipStreamSynchronize(st)); hc[0] = *u; }
@@ -357,11 +354,8 @@ template<class In> int merge_path(ald_tset_dev *s, In B, const int64_t *match, c
     if(d_slot.ensure(8 * (size_t)(N + 1)) || d_ecnt.ensure(8 * (size_t)(N + 1)) || d_scnt.ensure(8 * (size_t)(N + 1)) || Ob.ensure_items(N)) return ald_set_err(ALD_ERR_NOMEM, "resident set items");
     if(N > 0) hipLaunchKernelGGL(rs_slots, dim3(grid_for(nA + nB)), dim3(TX_BLOCK), 0, st, nA, nB, (const int32_t*)d_shift.p, match, ins, (const int32_t*)d_ub.p, (int64_t*)d_slot.p);
     hipLaunchKernelGGL(rs_sizes<In>, dim3(grid_for(N + 1)), dim3(TX_BLOCK), 0, st, A, B, (const int64_t*)d_slot.p, (const int64_t*)d_rmatch.p, N, (int64_t*)d_ecnt.p, (int64_t*)d_scnt.p);
-    size_t t3 = 0;
-    HCHK(hipcub::DeviceScan::ExclusiveSum(nullptr, t3, (const int64_t*)d_ecnt.p, (int64_t*)Ob.eoff.p, (int)(N + 1), st));
-    if(d_tmp.ensure(t3 + 256)) return ald_set_err(ALD_ERR_NOMEM, "resident set scan scratch");
-    HCHK(hipcub::DeviceScan::ExclusiveSum(d_tmp.p, t3, (const int64_t*)d_ecnt.p, (int64_t*)Ob.eoff.p, (int)(N + 1), st));
-    HCHK(hipcub::DeviceScan::ExclusiveSum(d_tmp.p, t3, (const int64_t*)d_scnt.p, (int64_t*)Ob.soff.p, (int)(N + 1), st));
+    { int rc = tx_cub(d_tmp, scan, [&](void *t, size_t &nb) { return hipcub::DeviceScan::ExclusiveSum(t, nb, (const int64_t*)d_ecnt.p, (int64_t*)Ob.eoff.p, (int)(N + 1), st); }); if(rc != ALD_OK) return rc; }
+    { int rc = tx_cub(d_tmp, scan, [&](void *t, size_t &nb) { return hipcub::DeviceScan::ExclusiveSum(t, nb, (const int64_t*)d_scnt.p, (int64_t*)Ob.soff.p, (int)(N + 1), st); }); if(rc != ALD_OK) return rc; }
     HCHK(hipMemcpyAsync(hc + 1, (const int64_t*)Ob.eoff.p + N, 8, hipMemcpyDeviceToHost, st));
     HCHK(hipMemcpyAsync(hc + 2, (const int64_t*)Ob.soff.p + N, 8, hipMemcpyDeviceToHost, st));
     HCHK(hipStreamSynchronize(st));
@@ -391,7 +385,7 @@ int add_records(ald_tset_dev *s, const uint32_t *d_pool, const unsigned long lon
     s->last_device_ms = 0;
     if(np == 0) return ALD_OK;
     hipStream_t st = s->st;
-    RedScratch S; S.red = s->red; S.pin = s->pin; S.st = st; S.d2h = &s->bytes_to_host;
+    RedScratch S; S.x = &s->tx; S.st = st; S.d2h = &s->bytes_to_host;
     TxIn in; in.roff = d_roff; in.pool = d_pool; in.np = np;
     TxFront X; X.ev0 = s->ev0;
     const unsigned long long *h_off = nullptr;             // != null: h_pool holds the single-exon records only, in the order of X.host_paths
@@ -403,11 +397,12 @@ int add_records(ald_tset_dev *s, const uint32_t *d_pool, const unsigned long lon
         { int rc = tx_front_heads(S, in, X); if(rc != ALD_OK) return rc; }
         if(!d_cov) h_cov = X.h_cov;
         h_roff = nullptr;
-        if(!skip_single_exon) { int rc = tx_compact_singles(S, in, X, s->w[14], &h_pool, &h_off); if(rc != ALD_OK) return rc; }      // read behind the stream waits below
+        if(!skip_single_exon) { int rc = tx_compact_singles(S, in, X, s->mg.singles, &h_pool, &h_off); if(rc != ALD_OK) return rc; }      // read behind the stream waits below
     }
     if(X.n_groups > 0) {
         const int64_t G = X.n_groups;
-        DevBuf &d_ghead = s->w[0], &d_perm = s->w[1], &d_match = s->w[2], &d_ins = s->w[3], &d_unm = s->w[4], &d_start = s->w[5], &d_sbeg = s->w[13], &d_lab = s->d_label, &d_ptid = s->d_tid;
+        MergeScratch &M = s->mg;
+        DevBuf &d_ghead = M.ghead, &d_perm = M.perm, &d_match = M.match, &d_ins = M.ins, &d_unm = M.unm, &d_start = M.start, &d_sbeg = M.sbeg, &d_lab = s->d_label, &d_ptid = s->d_tid;
         if(d_ghead.ensure(4 * (size_t)G) || d_perm.ensure(4 * (size_t)G) || d_match.ensure(8 * (size_t)G) || d_ins.ensure(8 * (size_t)G) || d_unm.ensure(4 * (size_t)(G + 1))
            || d_start.ensure(8 * (size_t)G) || d_sbeg.ensure(8 * (size_t)(G + 1)) || (label && d_lab.ensure(8 * (size_t)n_graphs + 8)) || (h_tid && !d_tid && d_ptid.ensure(8 * (size_t)np + 8)))
             return ald_set_err(ALD_ERR_NOMEM, "resident set batch scratch");
@@ -440,30 +435,27 @@ int add_device_stream(ald_tset_dev *s, const uint32_t *d_words, int64_t n_words,
 {
     hipStream_t st = s->st;
     StreamIndex I;
-    { const int rc = tx_stream_index(st, s->ix, s->pin_ix, s->ev_i0, s->ev_i1, d_words, n_words, graph_offset, I);
+    { const int rc = tx_stream_index(st, s->ix, s->ev_i0, s->ev_i1, d_words, n_words, graph_offset, I);
       s->bytes_to_host += 40; s->st_index_ms = I.ms;
       if(rc != ALD_OK) return rc; }
     const int64_t nt = I.nt, ng = I.ng;
     s->st_transcripts = nt; s->st_groups = ng;
-    DevBuf &d_len = s->sr[0], &d_at = s->sr[1], &d_keep = s->sr[2], &d_kord = s->sr[3], &d_tmp = s->sr[4], &d_covin = s->sr[5], &d_tidin = s->sr[6], &d_cov = s->sr[7], &d_tidk = s->sr[8];
+    StreamRecScratch &R = s->sr;
+    DevBuf &d_len = R.len, &d_at = R.at, &d_keep = R.keep, &d_kord = R.kord, &d_tmp = R.cub_tmp, &d_covin = R.cov_in, &d_tidin = R.tid_in, &d_cov = R.cov, &d_tidk = R.tid;
     // a scratch record has 6 words more than its transcript has in the stream (18 + k against 12 + k)
     if(d_len.ensure(8 * (size_t)(nt + 1)) || d_at.ensure(8 * (size_t)(nt + 1)) || d_keep.ensure(4 * (size_t)(nt + 1)) || d_kord.ensure(4 * (size_t)(nt + 1))
        || (coverage && (d_covin.ensure(8 * (size_t)nt) || d_cov.ensure(8 * (size_t)nt))) || (tid && (d_tidin.ensure(8 * (size_t)nt) || d_tidk.ensure(8 * (size_t)nt)))
-       || s->d_pool.ensure(4 * (size_t)(n_words + 6 * nt) + 64) || s->d_roff.ensure(8 * (size_t)nt + 8) || s->pin_sr.ensure(16 + 12 * (size_t)ng + 64)) return ald_set_err(ALD_ERR_NOMEM, "resident set stream buffers");
-    size_t b1 = 0, b2 = 0;
-    HCHK(hipcub::DeviceScan::ExclusiveSum(nullptr, b1, (const int64_t*)d_len.p, (int64_t*)d_at.p, (int)(nt + 1), st));
-    HCHK(hipcub::DeviceScan::ExclusiveSum(nullptr, b2, (const int32_t*)d_keep.p, (int32_t*)d_kord.p, (int)(nt + 1), st));
-    if(d_tmp.ensure(std::max(b1, b2) + 256)) return ald_set_err(ALD_ERR_NOMEM, "scan scratch");
+       || s->d_pool.ensure(4 * (size_t)(n_words + 6 * nt) + 64) || s->d_roff.ensure(8 * (size_t)nt + 8) || R.p_head.ensure(16 + 12 * (size_t)ng + 64)) return ald_set_err(ALD_ERR_NOMEM, "resident set stream buffers");
     if(coverage) HCHK(hipMemcpyAsync(d_covin.p, coverage, 8 * (size_t)nt, hipMemcpyHostToDevice, st));
     if(tid) HCHK(hipMemcpyAsync(d_tidin.p, tid, 8 * (size_t)nt, hipMemcpyHostToDevice, st));
     hipLaunchKernelGGL(sr_len, dim3(grid_for(nt + 1)), dim3(TX_BLOCK), 0, st, d_words, I.toff, nt, (int)(skip_single_exon != 0), (int64_t*)d_len.p, (int32_t*)d_keep.p);
-    HCHK(hipcub::DeviceScan::ExclusiveSum(d_tmp.p, b1, (const int64_t*)d_len.p, (int64_t*)d_at.p, (int)(nt + 1), st));
-    HCHK(hipcub::DeviceScan::ExclusiveSum(d_tmp.p, b2, (const int32_t*)d_keep.p, (int32_t*)d_kord.p, (int)(nt + 1), st));
+    { int rc = tx_cub(d_tmp, "scan scratch", [&](void *t, size_t &nb) { return hipcub::DeviceScan::ExclusiveSum(t, nb, (const int64_t*)d_len.p, (int64_t*)d_at.p, (int)(nt + 1), st); }); if(rc != ALD_OK) return rc; }
+    { int rc = tx_cub(d_tmp, "scan scratch", [&](void *t, size_t &nb) { return hipcub::DeviceScan::ExclusiveSum(t, nb, (const int32_t*)d_keep.p, (int32_t*)d_kord.p, (int)(nt + 1), st); }); if(rc != ALD_OK) return rc; }
     hipLaunchKernelGGL(sr_emit, dim3(grid_for(16 * nt)), dim3(TX_BLOCK), 0, st, d_words, I.toff, I.gid, (const int64_t*)d_at.p, (const int32_t*)d_kord.p, nt,
                        coverage ? (const double*)d_covin.p : (const double*)nullptr, tid ? (const int64_t*)d_tidin.p : (const int64_t*)nullptr,
                        (uint32_t*)s->d_pool.p, (unsigned long long*)s->d_roff.p, (double*)d_cov.p, (int64_t*)d_tidk.p);
     // to the host: the number of kept transcripts, label + sid of every group (12 bytes per group)
-    char *hp = (char*)s->pin_sr.p; int64_t *h_label = (int64_t*)(hp + 16); int32_t *h_sid = (int32_t*)(hp + 16 + 8 * (size_t)ng);
+    char *hp = (char*)R.p_head.p; int64_t *h_label = (int64_t*)(hp + 16); int32_t *h_sid = (int32_t*)(hp + 16 + 8 * (size_t)ng);
     HCHK(hipMemcpyAsync(hp, (const int32_t*)d_kord.p + nt, 4, hipMemcpyDeviceToHost, st));
     HCHK(hipMemcpyAsync(h_label, I.label, 8 * (size_t)ng, hipMemcpyDeviceToHost, st));
     HCHK(hipMemcpyAsync(h_sid, I.sid, 4 * (size_t)ng, hipMemcpyDeviceToHost, st));
@@ -474,14 +466,6 @@ int add_device_stream(ald_tset_dev *s, const uint32_t *d_words, int64_t n_words,
     // without the filter every transcript is kept and a path's ordinal is its ordinal in the stream: coverage[] / tid[] serve the host part as they are
     return add_records(s, (const uint32_t*)s->d_pool.p, (const unsigned long long*)s->d_roff.p, nullptr, nullptr, coverage, tid, np, (int)ng, h_sid, h_label, tid_base, skip_single_exon,
                        coverage ? (const double*)d_cov.p : (const double*)nullptr, tid ? (const int64_t*)d_tidk.p : (const int64_t*)nullptr);
-}
-
-int has_device(int32_t device)
-{
-    int ndev = 0;
-    if(hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return ald_set_err(ALD_ERR_NO_DEVICE, "no HIP device visible: the resident transcript set has no CPU fallback");
-    if(device < 0 || device >= ndev) return ald_set_err(ALD_ERR_INVALID, "device index out of range");
-    return ALD_OK;
 }
 
 // The device part, copied back: flat arrays in the set's order (exon / sample offsets included), count2 = #samples
@@ -556,7 +540,7 @@ int ald_tset_dev_create(int32_t device, double single_exon_overlap, ald_tset_dev
 {
     if(!out) return ALD_ERR_INVALID;
     *out = nullptr;
-    { int rc = has_device(device); if(rc != ALD_OK) return rc; }
+    { int rc = tx_need_device(device, "the resident transcript set"); if(rc != ALD_OK) return rc; }
     HCHK(hipSetDevice(device));
     std::unique_ptr<ald_tset_dev> s(new ald_tset_dev(single_exon_overlap));
     s->device = device;
@@ -646,7 +630,7 @@ int ald_tset_dev_merge(ald_tset_dev *dst, ald_tset_dev *src)
     dst->last_device_ms = 0;
     if(nB > 0) {
         hipStream_t st = dst->st;
-        DevBuf &d_match = dst->w[2], &d_ins = dst->w[3], &d_unm = dst->w[4];
+        DevBuf &d_match = dst->mg.match, &d_ins = dst->mg.ins, &d_unm = dst->mg.unm;
         if(d_match.ensure(8 * (size_t)nB) || d_ins.ensure(8 * (size_t)nB) || d_unm.ensure(4 * (size_t)(nB + 1))) return ald_set_err(ALD_ERR_NOMEM, "resident set merge scratch");
         HCHK(hipEventRecord(dst->ev0, st));
         InSet B; B.v = Sb.view(); B.n = nB;
