@@ -420,7 +420,7 @@ int ald_batch_upload(ald_batch *b)
     uint64_t pool = 0; for(int g = 0; g < n; g++) pool += 16ull * b->hb.g_ne[g] + 256;
     if(const char *ev = getenv("ALD_DEBUG_POOL_WORDS")) { const long long k = atoll(ev); if(k > 0 && (uint64_t)k < pool) pool = (uint64_t)k; }
     b->pool_cap_words = pool;
-    b->index_cap = pool / (REC_HDR_WORDS + 2) + 1;         // a record is at least a header and two vertices long
+    b->index_cap = pool / (ALD_REC_HDR + 2) + 1;         // a record is at least a header and two vertices long
     if(b->d_status.ensure(4 * (size_t)n + 4) || b->d_npaths.ensure(4 * (size_t)n + 4) || b->d_niters.ensure(4 * (size_t)n + 4) || b->d_pool.ensure(4 * pool + 64) || b->d_poolused.ensure(64)
        || b->d_index.ensure(8 * (size_t)b->index_cap + 64) || b->d_gfirst.ensure(8 * (size_t)n + 8))
         { hipStreamSynchronize(us); return set_err(ALD_ERR_NOMEM, "device output buffers"); }      // (the input copies are in flight: they read the batch's host arrays)
@@ -590,7 +590,7 @@ int end_run(ald_batch *b, EndStamps &T)
     uint64_t want = std::max<uint64_t>(2 * b->pool_cap_words, used + used / 4 + 4096);
     if(b->d_pool.ensure(4 * want + 64)) return set_err(ALD_ERR_NOMEM, "record pool");
     b->pool_cap_words = want;
-    b->index_cap = std::max<uint64_t>(want / (REC_HDR_WORDS + 2) + 1, iused + iused / 4 + 64);
+    b->index_cap = std::max<uint64_t>(want / (ALD_REC_HDR + 2) + 1, iused + iused / 4 + 64);
     if(b->d_index.ensure(8 * (size_t)b->index_cap + 64)) return set_err(ALD_ERR_NOMEM, "result index");
     int rc = start_run(b);
     if(rc != ALD_OK) return rc;
@@ -957,9 +957,8 @@ int ald_tset_add_batch(ald_tset *t, const ald_batch *b, const int32_t *sid, int6
 
 /* ---- finished transcripts as ONE self-contained stream: what ranks exchange in the multi-GPU gather and what a device list merges ----
  * 4-byte words, transcripts in ascending (graph, path index) order:
- *   [graph, path, sid, strand, count1, n_exons, weight f64, conf f64, abd f64, (l, r) * n_exons]        TS_HDR + 2 * n_exons words
+ *   [graph, path, sid, strand, count1, n_exons, weight f64, conf f64, abd f64, (l, r) * n_exons]        ALD_TS_HDR + 2 * n_exons words (record_layout.h)
  * Records of abandoned attempts and of graphs that did not end well are already gone (HostResults::build), exons are joined. */
-enum { TS_HDR = ALD_TS_HDR };
 int ald_batch_transcript_stream(const ald_batch *cb, const int32_t *sid, int32_t skip_single_exon, const uint32_t **words, int64_t *n_words)
 {
     if(!cb || !words || !n_words) return ALD_ERR_INVALID;
@@ -968,17 +967,15 @@ int ald_batch_transcript_stream(const ald_batch *cb, const int32_t *sid, int32_t
     const int64_t np = b->res.n_paths();
     const unsigned nthr = sink_threads(np);
     std::vector<int64_t> at((size_t)np + 1, 0);
-    for(int64_t i = 0; i < np; i++) { const int k = (int)b->res.rec(i)[REC_NEXW]; at[(size_t)i + 1] = at[(size_t)i] + ((k <= 2 && skip_single_exon) ? 0 : TS_HDR + k); }
+    for(int64_t i = 0; i < np; i++) { const int k = (int)b->res.rec(i)[ALD_REC_NEXW]; at[(size_t)i + 1] = at[(size_t)i] + ((k <= 2 && skip_single_exon) ? 0 : ALD_TS_HDR + k); }
     b->tstream.resize((size_t)at[(size_t)np] + 2);
     uint32_t *out = b->tstream.data();
     HostBatch::run_threads(nthr, [&](unsigned th) {
         for(int64_t i = np * th / nthr; i < np * (th + 1) / nthr; i++) {
             if(at[(size_t)i + 1] == at[(size_t)i]) continue;
-            const PathRec p = b->res.path((int64_t)((size_t)i)); uint32_t *w = out + at[(size_t)i];
-            w[0] = (uint32_t)p.graph; w[1] = (uint32_t)p.index; w[2] = (uint32_t)(sid ? sid[p.graph] : -1); w[3] = (uint32_t)(unsigned char)p.strand;
-            w[4] = (uint32_t)p.count; w[5] = (uint32_t)(p.nexw / 2);
-            memcpy(w + 6, &p.weight, 8); memcpy(w + 8, &p.conf, 8); memcpy(w + 10, &p.abd, 8);
-            if(p.nexw) memcpy(w + TS_HDR, b->res.exons(p), 4 * (size_t)p.nexw);
+            const uint32_t *r = b->res.rec(i); uint32_t *w = out + at[(size_t)i];
+            for(int l = 0; l < ALD_TS_HDR; l++) w[l] = ts_header_word(r, l, sid);
+            if(r[ALD_REC_NEXW]) memcpy(w + ALD_TS_HDR, rec_exons(r), 4 * (size_t)r[ALD_REC_NEXW]);
         }
     });
     *words = out; *n_words = at[(size_t)np];
@@ -992,7 +989,7 @@ int ald_tset_add_stream(ald_tset *t, const uint32_t *words, int64_t n_words, int
     // record boundaries and groups (one serial walk: the lengths are in the records)
     std::vector<int64_t> offs, grp; std::vector<int32_t> grp_sid;
     { int rc = tx_walk_stream(words, n_words, [&](int64_t o, bool first) {
-          if(first) { grp.push_back((int64_t)offs.size()); grp_sid.push_back((int32_t)words[o + 2]); }
+          if(first) { grp.push_back((int64_t)offs.size()); grp_sid.push_back((int32_t)words[o + ALD_TS_SID]); }
           offs.push_back(o);
       }); if(rc != ALD_OK) return rc; }
     const int64_t nt = (int64_t)offs.size(); grp.push_back(nt);
@@ -1000,16 +997,15 @@ int ald_tset_add_stream(ald_tset *t, const uint32_t *words, int64_t n_words, int
     const auto T1 = std::chrono::steady_clock::now();
     std::vector<uint32_t> bucket((size_t)nt);
     HostBatch::run_threads(nthr, [&](unsigned th) {
-        for(int64_t i = nt * th / nthr; i < nt * (th + 1) / nthr; i++) { const uint32_t *w = words + offs[(size_t)i]; bucket[(size_t)i] = (uint32_t)aletsch::sink_transcript::chain_key((const int32_t*)(w + TS_HDR), 2 * (size_t)w[5]); }
+        for(int64_t i = nt * th / nthr; i < nt * (th + 1) / nthr; i++) { const uint32_t *w = words + offs[(size_t)i]; bucket[(size_t)i] = (uint32_t)aletsch::sink_transcript::chain_key(ts_exons(w), (size_t)ts_nexw(w)); }
     });
     const auto T2 = std::chrono::steady_clock::now();
     merge_groups(t, nthr, (int64_t)grp_sid.size(), grp.data(), grp_sid.data(), bucket.data(), [&](int64_t i, aletsch::sink_transcript &x) {
         const uint32_t *w = words + offs[(size_t)i];
-        double weight, conf, abd; memcpy(&weight, w + 6, 8); memcpy(&conf, w + 8, 8); memcpy(&abd, w + 10, 8);
-        x.strand = (char)w[3]; x.coverage = log(1.0 + weight); x.top.cov2 = x.coverage; x.top.conf = conf; x.top.abd = abd; x.top.count1 = (int32_t)w[4]; x.count2 = 1;
-        x.tid = tid_base + ((((int64_t)w[0] + graph_offset) << 20) | (int64_t)w[1]);
-        x.xs.assign((const int32_t*)(w + TS_HDR), (const int32_t*)(w + TS_HDR) + 2 * (size_t)w[5]);
-    }, [&](int64_t i) { __builtin_prefetch(words + offs[(size_t)i]); __builtin_prefetch(words + offs[(size_t)i] + 16); });
+        x.strand = (char)w[ALD_TS_STRAND]; x.coverage = log(1.0 + ts_f64(w, ALD_TS_WEIGHT)); x.top.cov2 = x.coverage; x.top.conf = ts_f64(w, ALD_TS_CONF); x.top.abd = ts_f64(w, ALD_TS_ABD); x.top.count1 = (int32_t)w[ALD_TS_COUNT1]; x.count2 = 1;
+        x.tid = tid_base + ((((int64_t)w[ALD_TS_GRAPH] + graph_offset) << 20) | (int64_t)w[ALD_TS_PATH]);
+        x.xs.assign(ts_exons(w), ts_exons(w) + ts_nexw(w));
+    }, [&](int64_t i) { const uint32_t *w = words + offs[(size_t)i]; __builtin_prefetch(w); __builtin_prefetch((const char*)w + 64); });
     if(getenv("ALD_SINK_PROF")) { const auto T3 = std::chrono::steady_clock::now(); auto ms = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point c) { return std::chrono::duration<double, std::milli>(c - a).count(); };
         fprintf(stderr, "[sink] stream of %lld transcripts: boundaries %.1f ms, hash pass %.1f ms, merge pass %.1f ms (%u threads)\n", (long long)nt, ms(T0, T1), ms(T1, T2), ms(T2, T3), nthr); }
     return ALD_OK;
@@ -1063,10 +1059,11 @@ int ald_records_add_graph_offset(uint32_t *words, int64_t n_words, int32_t graph
 {
     if((!words && n_words > 0) || n_words < 0) return ALD_ERR_INVALID;
     int64_t o = 0;
-    while(o + REC_HDR_WORDS <= n_words) {
-        words[o] += (uint32_t)graph_offset;
-        const int64_t w = (int64_t)rec_words(words[o + 2], words[o + REC_NEXW]);
-        if(words[o + 2] < 2 || o + w > n_words) return set_err(ALD_ERR_INVALID, "malformed record stream");
+    while(o + ALD_REC_HDR <= n_words) {
+        uint32_t *r = words + o;
+        r[ALD_REC_GRAPH] += (uint32_t)graph_offset;
+        const int64_t w = (int64_t)rec_words(r[ALD_REC_NV], r[ALD_REC_NEXW]);
+        if(r[ALD_REC_NV] < 2 || o + w > n_words) return set_err(ALD_ERR_INVALID, "malformed record stream");
         o += w;
     }
     return ALD_OK;

@@ -3,6 +3,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include "host_pack.h"
+#include "record_layout.h"
 #include "../host/transcript_sink.hpp"
 #include <string>
 #include <vector>
@@ -166,7 +167,6 @@ struct ald_batch {
 
 // The result sink behind ald_tset_*.  Buckets (intron-chain hashes) never interact: the set is kept as NSHARD independent tables, bucket h
 // in table h % NSHARD, so that a whole batch can be merged by NSHARD host threads without a lock; the export walks all keys in ascending order.
-enum { ALD_TS_HDR = 12 };          // words in front of a transcript's exons in a transcript stream (ald_batch_transcript_stream)
 enum { ALD_TSET_SHARDS = 16 };
 struct ald_tset {
     std::vector<aletsch::transcript_sink> shard; double overlap;

@@ -9,6 +9,7 @@
 #include <float.h>
 #include <limits.h>
 #include "../../include/aletsch_decomp.h"
+#include "record_layout.h"      // the path record the kernel writes: its words (ALD_REC_*), rec_words()
 
 #ifdef ALD_EMU
   // single-lane emulation of the engine, compiled ONLY by tests/kernel_emu (never part of the product library)
@@ -166,18 +167,6 @@ enum { OP_BROKEN = 1, OP_TRIVIAL_FAST = 2, OP_TRIVIAL_NOW = 3, OP_TRIVIAL_BEST =
        OP_UNSPLIT_NOW = 7, OP_UNSPLIT_BEST = 8, OP_GREEDY = 9, OP_COLLECT = 10 };
 enum { HF_OCC = 1, HF_LEXT = 2, HF_REXT = 4 };
 enum { NZ_MEMBER = 1, NZ_MEMO_VALID = 2, NZ_MEMO_TYPE_SHIFT = 2 /* 3 bits */, NZ_MEMO_DEG_GT1 = 32 };      // bits of Hot::nz
-// path record (4-byte words): [0]=graph [1]=path index [2]=#vertices [3]=length [4]=count [5]=strand char | attempt << 8
-//                             [6..13] = weight, abd, conf, reads (f64)   [14] = #exon words (2 per exon)   [15] = 0
-//                             [16..16+nv) vertices, then the exon words (l, r)* of the transcript the path becomes -- touching
-//                             vertex intervals joined, empty ones dropped (essential.cc:719-748) --, padded to an even word count
-enum { REC_HDR_WORDS = 16, REC_NEXW = 14 };
-#if defined(__HIP__)
-  #define ALD_HD __host__ __device__
-#else
-  #define ALD_HD
-#endif
-ALD_HD static inline unsigned long long rec_words(unsigned nv, unsigned nexw) { unsigned long long w = (unsigned long long)REC_HDR_WORDS + nv + nexw; return w + (w & 1); }
-
 // ---- wire format as the kernel sees it: device pointers into ONE coalesced HBM buffer ----
 struct BatchIn {
     int32_t n_graphs;

@@ -3116,17 +3116,17 @@ ALD_FN void collect_path(int e)
         if(C.ed[e].estrand == 1) st = '+';
         if(C.ed[e].estrand == 2) st = '-';
         if(st == '.') st = HC.gstrand;
-        r[0] = (uint32_t)HC.g; r[1] = (uint32_t)HC.n_paths; r[2] = (uint32_t)nvp; r[3] = (uint32_t)mi; r[4] = (uint32_t)uni(C.ed[e].ecount); r[5] = (uint32_t)st | ((uint32_t)(A->attempt & 0xFF) << 8);
-        ALD_GLOBAL double *d = (ALD_GLOBAL double*)(r + 6);
-        d[0] = uni(H.ed[e].w); d[1] = uni(C.ed[e].eabd); d[2] = exp(C.ed[e].econf); d[3] = uni(C.ed[e].med);
-        ALD_GLOBAL uint32_t *pv = r + REC_HDR_WORDS; int w = 0;
+        r[ALD_REC_GRAPH] = (uint32_t)HC.g; r[ALD_REC_PATH] = (uint32_t)HC.n_paths; r[ALD_REC_NV] = (uint32_t)nvp; r[ALD_REC_LENGTH] = (uint32_t)mi; r[ALD_REC_COUNT] = (uint32_t)uni(C.ed[e].ecount); r[ALD_REC_STRAND] = (uint32_t)st | ((uint32_t)(A->attempt & 0xFF) << 8);
+        ALD_GLOBAL double *d = (ALD_GLOBAL double*)(r + ALD_REC_WEIGHT);
+        d[rec_f64_slot(ALD_REC_WEIGHT)] = uni(H.ed[e].w); d[rec_f64_slot(ALD_REC_ABD)] = uni(C.ed[e].eabd); d[rec_f64_slot(ALD_REC_CONF)] = exp(C.ed[e].econf); d[rec_f64_slot(ALD_REC_READS)] = uni(C.ed[e].med);
+        ALD_GLOBAL uint32_t *pv = r + ALD_REC_HDR; int w = 0;
         pv[w++] = 0;
         for(int k = 0; k < NW; k++) { uint64_t mk = uni(C.ed[e].mask[k]); while(mk) { int b = ffs64(mk); mk &= mk - 1; pv[w++] = (uint32_t)(k * 64 + b); } }
         pv[w++] = (uint32_t)n;
-        r[REC_NEXW] = (uint32_t)nexw; r[REC_NEXW + 1] = 0;
+        r[ALD_REC_NEXW] = (uint32_t)nexw; r[ALD_REC_NEXW + 1] = 0;
         { int q = 0; for(int k = 0; k < NW; k++) { uint64_t mk = uni(C.ed[e].mask[k]); while(mk) { int b = ffs64(mk); mk &= mk - 1; int x = k * 64 + b; const int l = uni(C.vx[x].lpos), rr = uni(C.vx[x].rpos);
             if(l >= rr) continue; if(q > 0 && (int)pv[w + q - 1] == l) pv[w + q - 1] = (uint32_t)rr; else { pv[w + q] = (uint32_t)l; pv[w + q + 1] = (uint32_t)rr; q += 2; } } } w += q; }
-        if((REC_HDR_WORDS + nvp + nexw) & 1) pv[w] = 0;
+        if((ALD_REC_HDR + nvp + nexw) & 1) pv[w] = 0;
         if(tracing()) { int save = HC.n_iters; trace(OP_COLLECT, (int)uni(H.eid[e]), nvp, uni(H.ed[e].w)); HC.n_iters = save; }
         HC.n_paths++;
     }
@@ -3213,17 +3213,17 @@ ALD_FN void collect_existing_st_paths()
         if(C.ed[e].estrand == 1) st = '+';
         if(C.ed[e].estrand == 2) st = '-';
         if(st == '.') st = HC.gstrand;
-        r[0] = (uint32_t)HC.g; r[1] = (uint32_t)(HC.n_paths + rank); r[2] = (uint32_t)nvp; r[3] = (uint32_t)C.ed[e].mei; r[4] = (uint32_t)C.ed[e].ecount; r[5] = (uint32_t)st | ((uint32_t)(A->attempt & 0xFF) << 8);
-        ALD_GLOBAL double *d = (ALD_GLOBAL double*)(r + 6);
-        d[0] = H.ed[e].w; d[1] = C.ed[e].eabd; d[2] = exp(C.ed[e].econf); d[3] = C.ed[e].med;
-        ALD_GLOBAL uint32_t *pv = r + REC_HDR_WORDS; int w = 0;
+        r[ALD_REC_GRAPH] = (uint32_t)HC.g; r[ALD_REC_PATH] = (uint32_t)(HC.n_paths + rank); r[ALD_REC_NV] = (uint32_t)nvp; r[ALD_REC_LENGTH] = (uint32_t)C.ed[e].mei; r[ALD_REC_COUNT] = (uint32_t)C.ed[e].ecount; r[ALD_REC_STRAND] = (uint32_t)st | ((uint32_t)(A->attempt & 0xFF) << 8);
+        ALD_GLOBAL double *d = (ALD_GLOBAL double*)(r + ALD_REC_WEIGHT);
+        d[rec_f64_slot(ALD_REC_WEIGHT)] = H.ed[e].w; d[rec_f64_slot(ALD_REC_ABD)] = C.ed[e].eabd; d[rec_f64_slot(ALD_REC_CONF)] = exp(C.ed[e].econf); d[rec_f64_slot(ALD_REC_READS)] = C.ed[e].med;
+        ALD_GLOBAL uint32_t *pv = r + ALD_REC_HDR; int w = 0;
         pv[w++] = 0;
         for(int k = 0; k < NW; k++) { uint64_t mk = C.ed[e].mask[k]; while(mk) { int b = ffs64(mk); mk &= mk - 1; pv[w++] = (uint32_t)(k * 64 + b); } }
         pv[w++] = (uint32_t)nlast;
-        r[REC_NEXW] = (uint32_t)nexw; r[REC_NEXW + 1] = 0;
+        r[ALD_REC_NEXW] = (uint32_t)nexw; r[ALD_REC_NEXW + 1] = 0;
         { int q = 0; for(int k = 0; k < NW; k++) { uint64_t mk = C.ed[e].mask[k]; while(mk) { int b = ffs64(mk); mk &= mk - 1; int x = k * 64 + b; const int l = C.vx[x].lpos, rr = C.vx[x].rpos;
             if(l >= rr) continue; if(q > 0 && (int)pv[w + q - 1] == l) pv[w + q - 1] = (uint32_t)rr; else { pv[w + q] = (uint32_t)l; pv[w + q + 1] = (uint32_t)rr; q += 2; } } } w += q; }
-        if((REC_HDR_WORDS + nvp + nexw) & 1) pv[w] = 0;
+        if((ALD_REC_HDR + nvp + nexw) & 1) pv[w] = 0;
     }
     const bool any_bad = wballot(bad) != 0, any_full = wballot(full) != 0;
     wsync_mem();

@@ -576,7 +576,7 @@ struct HostBatch {
 
 // ---- results ----
 // One decoded path record (a VIEW, made on demand from the record words: HostResults::path).  vert_off: word offset of its vertex list
-// in the record pool; the exon words of the transcript it becomes follow the vertices (decomp_common.h: record layout);
+// in the record pool; the exon words of the transcript it becomes follow the vertices (record_layout.h);
 // coverage = log(1 + weight) (essential.cc:725), taken with the host's libm.
 struct PathRec { int32_t graph, index, nv, length, count, nexw; char strand; int attempt; double weight, abd, conf, reads, coverage; uint64_t vert_off; };
 struct HostResults {
@@ -599,10 +599,10 @@ struct HostResults {
     PathRec path(int64_t i) const
     {
         const uint32_t *r = rec(i); PathRec p;
-        p.graph = (int32_t)r[0]; p.index = (int32_t)r[1]; p.nv = (int32_t)r[2]; p.length = (int32_t)r[3]; p.count = (int32_t)r[4]; p.nexw = (int32_t)r[REC_NEXW];
-        p.strand = (char)(r[5] & 0xFF); p.attempt = (int)((r[5] >> 8) & 0xFF);
-        memcpy(&p.weight, r + 6, 8); memcpy(&p.abd, r + 8, 8); memcpy(&p.conf, r + 10, 8); memcpy(&p.reads, r + 12, 8);
-        p.coverage = coverage[(size_t)i]; p.vert_off = rec_off[(size_t)i] + REC_HDR_WORDS;
+        p.graph = (int32_t)r[ALD_REC_GRAPH]; p.index = (int32_t)r[ALD_REC_PATH]; p.nv = (int32_t)r[ALD_REC_NV]; p.length = (int32_t)r[ALD_REC_LENGTH]; p.count = (int32_t)r[ALD_REC_COUNT]; p.nexw = (int32_t)r[ALD_REC_NEXW];
+        p.strand = (char)rec_strand(r); p.attempt = (int)rec_attempt(r);
+        p.weight = rec_f64(r, ALD_REC_WEIGHT); p.abd = rec_f64(r, ALD_REC_ABD); p.conf = rec_f64(r, ALD_REC_CONF); p.reads = rec_f64(r, ALD_REC_READS);
+        p.coverage = coverage[(size_t)i]; p.vert_off = rec_off[(size_t)i] + ALD_REC_HDR;
         return p;
     }
 
@@ -634,17 +634,16 @@ struct HostResults {
             int g2 = g;                                                               // the record eight paths ahead is asked for now: records lie in the pool
             for(int64_t i = lo; i < hi; i++) {                                        // in the order the waves emitted them, every one is a miss of its own
                 while(path_begin[(size_t)g + 1] <= i) g++;
-                if(i + 8 < hi) { while(path_begin[(size_t)g2 + 1] <= i + 8) g2++; const uint64_t o2 = index[(uint64_t)graph_first[g2] + (uint64_t)(i + 8 - path_begin[(size_t)g2])]; if(o2 + REC_HDR_WORDS <= W) { __builtin_prefetch(pw + o2); __builtin_prefetch(pw + o2 + 16); } }
+                if(i + 8 < hi) { while(path_begin[(size_t)g2 + 1] <= i + 8) g2++; const uint64_t o2 = index[(uint64_t)graph_first[g2] + (uint64_t)(i + 8 - path_begin[(size_t)g2])]; if(o2 + ALD_REC_HDR <= W) { __builtin_prefetch(pw + o2); __builtin_prefetch(pw + o2 + ALD_REC_HDR); } }
                 const int32_t idx = (int32_t)(i - path_begin[(size_t)g]);
                 const uint64_t o = index[(uint64_t)graph_first[g] + (uint64_t)idx];
-                if(o + REC_HDR_WORDS > W) { bad[t] = 1; return; }
+                if(o + ALD_REC_HDR > W) { bad[t] = 1; return; }
                 const uint32_t *r = pw + o;
-                const uint32_t nv = r[2], nexw = r[REC_NEXW];
-                if(nv < 2 || (nexw & 1) || nexw > 2 * nv || o + rec_words(nv, nexw) > W || (int32_t)r[0] != g || (int32_t)r[1] != idx) { bad[t] = 2; return; }
-                double w; memcpy(&w, r + 6, 8);
-                rec_off[(size_t)i] = o; coverage[(size_t)i] = log(1.0 + w);
-                chain_key[(size_t)i] = (uint32_t)aletsch::sink_transcript::chain_key((const int32_t*)(r + REC_HDR_WORDS + nv), (size_t)nexw); n_exon_words[(size_t)i] = (uint16_t)(nexw < 65535u ? nexw : 65535u);
-                if(idx == 0) attempt[(size_t)g] = (int)((r[5] >> 8) & 0xFF);
+                const uint32_t nv = r[ALD_REC_NV], nexw = r[ALD_REC_NEXW];
+                if(nv < 2 || (nexw & 1) || nexw > 2 * nv || o + rec_words(nv, nexw) > W || (int32_t)r[ALD_REC_GRAPH] != g || (int32_t)r[ALD_REC_PATH] != idx) { bad[t] = 2; return; }
+                rec_off[(size_t)i] = o; coverage[(size_t)i] = log(1.0 + rec_f64(r, ALD_REC_WEIGHT));
+                chain_key[(size_t)i] = (uint32_t)aletsch::sink_transcript::chain_key(rec_exons(r), (size_t)nexw); n_exon_words[(size_t)i] = (uint16_t)(nexw < 65535u ? nexw : 65535u);
+                if(idx == 0) attempt[(size_t)g] = (int)rec_attempt(r);
                 obt += 4ll * nv + 40;
             }
             ob[t] = obt;

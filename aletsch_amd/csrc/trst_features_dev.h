@@ -82,7 +82,7 @@ ALD_INL int32_t *ft_junc(const FeatArgs &A, int32_t *lds, bool in_lds, int np, l
     if(in_lds) { nj = lds[2 * p + 1]; return lds + 2 * np + lds[2 * p]; }
     const unsigned long long o = A.index[gf + p];
     nj = A.scratch[2 * o];
-    return A.scratch + 2 * (o + REC_HDR_WORDS);
+    return A.scratch + 2 * (o + ALD_REC_HDR);
 }
 
 // ratio_of of the host routine: the junction weight over the smaller of the two flanking within-exon edges; a missing edge is the assert
@@ -195,21 +195,21 @@ template<bool RAW> ALD_INL void features_graph_t(const FeatArgs &A, int g, int32
 
     // ---- where the junction lists go: LDS when (offset, count) per path + the most junctions every path can have fit
     int bound = 0;
-    for(int p = lane; p < np; p += ALD_WAVE) { const int nv = (int)A.pool[A.index[gf + p] + 2]; bound += nv > 3 ? nv - 3 : 0; }
+    for(int p = lane; p < np; p += ALD_WAVE) { const int nv = (int)A.pool[A.index[gf + p] + ALD_REC_NV]; bound += nv > 3 ? nv - 3 : 0; }
     for(int off = ALD_WAVE / 2; off >= 1; off >>= 1) bound += wshfl(bound, lane ^ off);
     const bool in_lds = (int64_t)2 * np + 2 * (int64_t)bound <= (int64_t)A.lds_words;
     if(!in_lds && !A.scratch) { if(lane == 0) A.graph_rc[g] = ALD_ERR_NOMEM; return; }    // (the host sizes the scratch so that this is never taken)
     if(in_lds && lane == 0) {
         int acc = 0;
-        for(int p = 0; p < np; p++) { lds[2 * p] = 2 * acc; const int nv = (int)A.pool[A.index[gf + p] + 2]; acc += nv > 3 ? nv - 3 : 0; }
+        for(int p = 0; p < np; p++) { lds[2 * p] = 2 * acc; const int nv = (int)A.pool[A.index[gf + p] + ALD_REC_NV]; acc += nv > 3 ? nv - 3 : 0; }
     }
     wsync();
     // ---- path::junc: consecutive INTERNAL vertices that do not touch.  A vertex outside the graph (never written by the kernel) makes the
     // path's list empty; its row then reports the assert below.
     for(int p = lane; p < np; p += ALD_WAVE) {
         const unsigned long long o = A.index[gf + p];
-        ALD_GLOBAL const uint32_t *pv = A.pool + o + REC_HDR_WORDS; const int n = (int)A.pool[o + 2];
-        int32_t *J = in_lds ? lds + 2 * np + lds[2 * p] : A.scratch + 2 * (o + REC_HDR_WORDS);
+        ALD_GLOBAL const uint32_t *pv = A.pool + o + ALD_REC_HDR; const int n = (int)A.pool[o + ALD_REC_NV];
+        int32_t *J = in_lds ? lds + 2 * np + lds[2 * p] : A.scratch + 2 * (o + ALD_REC_HDR);
         bool inside = true;
         for(int i = 0; i < n; i++) if(pv[i] >= (uint32_t)G.V) inside = false;
         int nj = 0;
@@ -222,7 +222,7 @@ template<bool RAW> ALD_INL void features_graph_t(const FeatArgs &A, int g, int32
     bool bad = false;
     for(int pid = lane; pid < np; pid += ALD_WAVE) {
         const unsigned long long o = A.index[gf + pid];
-        ALD_GLOBAL const uint32_t *pv = A.pool + o + REC_HDR_WORDS; const int n = (int)A.pool[o + 2];
+        ALD_GLOBAL const uint32_t *pv = A.pool + o + ALD_REC_HDR; const int n = (int)A.pool[o + ALD_REC_NV];
         ald_trst_features F = {};
         int done = 0;
         bool inside = true;

@@ -13,10 +13,9 @@ static const uint64_t TX_HOST = ~0ull;                 // key of a transcript th
 inline unsigned grid_for(int64_t n) { return (unsigned)((n + TX_BLOCK - 1) / TX_BLOCK); }
 
 // The paths of a batch as the kernels see them: record offsets in (graph, path) order + the record pool.  A record carries the joined
-// exons of its transcript behind the vertex list (decomp_common.h), written by the decomposition kernel, so nothing here needs the
+// exons of its transcript behind the vertex list (record_layout.h), written by the decomposition kernel, so nothing here needs the
 // staged graphs or a host-side parse.
 struct TxIn { const unsigned long long *roff; const uint32_t *pool; int64_t np; };
-__host__ __device__ inline const int32_t *rec_exons(const uint32_t *r) { return (const int32_t*)(r + REC_HDR_WORDS + r[2]); }
 
 // transcript::get_intron_chain_hashing (transcript.cc:183-201, util.cc:38-46) over the flat exon words; 64-bit size_t arithmetic as on the host
 __host__ __device__ inline uint64_t chain_key_dev(const int32_t *x, int n_words)
@@ -92,7 +91,7 @@ inline TxSample *tx_samples(const RedScratch &S) { return (TxSample*)S.x->sample
 // (host libm), sid: sample per graph or null.  Enqueued on S.st; returns after the counts are on the host.
 int tx_front_groups(RedScratch S, TxIn in, const double *h_cov, int n_graphs, const int32_t *sid, TxFront &F);
 // tx_front_groups in its two halves, for a caller without a host copy of the records (a batch that ald_batch_finish ended):
-//   tx_front_sort      keys + the stable sort, ENQUEUED only.  h_cov = null: the key pass also writes weight[p] (record word 6) into a dense
+//   tx_front_sort      keys + the stable sort, ENQUEUED only.  h_cov = null: the key pass also writes weight[p] (ALD_REC_WEIGHT) into a dense
 //                      array in (graph, path) order (weight), 8 bytes per path go to pinned memory (p_weight) and F.ev_w is recorded
 //   tx_front_coverage  waits for F.ev_w, takes log(1 + w) with the host's libm on up to 16 threads (ALD_SINK_THREADS) WHILE THE SORT RUNS, and
 //                      enqueues the upload to where tx_front_groups puts h_cov (cov): coverage is first read by tx_fold
@@ -121,9 +120,9 @@ template<class F> int tx_walk_stream(const uint32_t *words, int64_t n_words, F e
     int64_t last = -1;
     for(int64_t o = 0; o < n_words; ) {
         if(o + ALD_TS_HDR > n_words) return ald_set_err(ALD_ERR_INVALID, "malformed transcript stream");
-        const int64_t len = ALD_TS_HDR + 2 * (int64_t)words[o + 5];
-        if((int32_t)words[o + 5] < 0 || o + len > n_words) return ald_set_err(ALD_ERR_INVALID, "malformed transcript stream");
-        const int64_t g = (int64_t)words[o];
+        const uint32_t *w = words + o; const int64_t len = ts_words(w);
+        if((int32_t)w[ALD_TS_NEXONS] < 0 || o + len > n_words) return ald_set_err(ALD_ERR_INVALID, "malformed transcript stream");
+        const int64_t g = (int64_t)w[ALD_TS_GRAPH];
         if(g < last) return ald_set_err(ALD_ERR_INVALID, "transcript stream not in ascending graph order");
         each(o, g != last);
         last = g; o += len;
@@ -133,7 +132,7 @@ template<class F> int tx_walk_stream(const uint32_t *words, int64_t n_words, F e
 // The same walk on the device (tset_index.hip): the transcript boundaries of a stream in DEVICE memory by pointer doubling over the record
 // lengths.  toff[i] = first word of transcript i, toff[nt] = n_words; gid[i] = 1-based run of equal graph ids transcript i belongs to
 // (runs counted before any single-exon filter, as tx_stream_records pushes label / sid before it skips); label[k] = graph id of run k +
-// graph_offset, sid[k] = word 2 of its first transcript.  All four live in X (the caller's) until the next call.
+// graph_offset, sid[k] = ALD_TS_SID of its first transcript.  All four live in X (the caller's) until the next call.
 // Kernels on `st`; ONE copy of 40 bytes (counts + flags, into X.p_sum) and one synchronisation.  e0 / e1 (optional): recorded around the
 // kernels, ms = the time between them.  Malformed or descending: ALD_ERR_INVALID as tx_stream_records; n_words == 0 launches nothing;
 // n_words >= 2^31: ALD_ERR_INVALID (the callers keep the host walk for such a stream).

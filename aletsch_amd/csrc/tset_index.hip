@@ -1,7 +1,7 @@
 // tset_index.hip -- the transcript boundaries of a stream that lies in device memory, found without the host's record walk.
 //
 // A transcript stream (format of ald_batch_transcript_stream) has no index: record i + 1 begins where record i ends, and a record's length
-// is in its own header, len = 12 + 2 * words[o + 5].  The host walks it record by record (tx_stream_records).  But "the next record" is a
+// is in its own header (ts_words: ALD_TS_HDR + 2 * n_exons).  The host walks it record by record (tx_stream_records).  But "the next record" is a
 // function EVERY word position can evaluate by itself, and the real boundaries are what that function reaches from position 0: list
 // ranking.  Lengths are even, so only even positions are candidates; position o = 2 h is node h, and two extra nodes that point to
 // themselves end every chain: END (= n_words, the stream is consumed exactly) and BAD (a header that does not fit, a negative count, a
@@ -12,13 +12,13 @@
 //   ix_succ     1 lane / node        successor in 64-bit arithmetic, never reading past n_words; mark = {node 0}
 //   ix_jump     1 lane / node        one round of pointer doubling: a marked node marks its successor, then succ <- succ o succ, read from
 //                                    the previous round's buffer and written to the other.  After round k everything within 2^k - 1 links
-//                                    of position 0 is marked; a chain has at most n_words / 12 + 1 links, which fixes the number of rounds.
+//                                    of position 0 is marked; a chain has at most n_words / ALD_TS_HDR + 1 links, which fixes the number of rounds.
 //                                    (A mark set in this round and seen by another lane of the same round only marks a node early that a
 //                                    later round would mark anyway: marks only ever go to nodes position 0 reaches.)
 //   select      hipCUB               marked positions in ascending order: toff[0 .. nt)
 //   ix_graphs   1 lane / transcript  graph id (unsigned, as the host walk widens it), head of a run of equal ids, descending pair -> flag
 //   scan        hipCUB               inclusive sum of the heads: 1-based group of every transcript (counted BEFORE any single-exon filter)
-//   ix_labels   1 lane / transcript  label[group] = graph id + graph_offset, sid[group] = word 2 of the run's first transcript; the counts
+//   ix_labels   1 lane / transcript  label[group] = graph id + graph_offset, sid[group] = ALD_TS_SID of the run's first transcript; the counts
 //                                    and the flags into one small block that goes to the host in a single copy
 #include "tset_front.h"
 #include <hipcub/hipcub.hpp>
@@ -37,9 +37,9 @@ __global__ void ix_succ(const uint32_t *words, int64_t n_words, uint32_t M, uint
     if(i < (int64_t)M) {
         const int64_t o = 2 * i; nx = M + 1;
         if(o + ALD_TS_HDR <= n_words) {
-            const uint32_t c = words[o + 5];
-            const int64_t t = o + ALD_TS_HDR + 2 * (int64_t)c;
-            if((int32_t)c >= 0 && t <= n_words) nx = (uint32_t)(t >> 1);
+            const uint32_t *w = words + o;
+            const int64_t t = o + ts_words(w);
+            if((int32_t)w[ALD_TS_NEXONS] >= 0 && t <= n_words) nx = (uint32_t)(t >> 1);
         }
     }
     succ[i] = nx; mark[i] = i == 0 ? 1 : 0;
@@ -62,9 +62,9 @@ __global__ void ix_graphs(const uint32_t *words, int64_t n_words, unsigned long 
     const int64_t nt = (int64_t)sum[0];
     if(i == 0) toff[nt] = (unsigned long long)n_words;
     if(i >= nt) { head[i] = 0; return; }                     // (the scan runs over all `cap` entries: no count has to reach the host first)
-    const uint32_t g = words[toff[i]];
+    const uint32_t g = words[toff[i] + ALD_TS_GRAPH];
     if(i == 0) { head[i] = 1; return; }
-    const uint32_t pg = words[toff[i - 1]];
+    const uint32_t pg = words[toff[i - 1] + ALD_TS_GRAPH];
     head[i] = g != pg ? 1 : 0;
     if(g < pg) sum[4] = 1;
 }
@@ -77,8 +77,8 @@ __global__ void ix_labels(const uint32_t *words, int64_t n_words, const unsigned
     if(i == 0) { sum[1] = nt > 0 ? (unsigned long long)gid[nt - 1] : 0; sum[2] = mark[M]; sum[3] = mark[M + 1]; }
     if(i >= nt || !head[i]) return;
     const int64_t o = (int64_t)toff[i]; const int32_t k = gid[i] - 1;
-    label[k] = (int64_t)words[o] + graph_offset;
-    sid[k] = o + 2 < n_words ? (int32_t)words[o + 2] : 0;   // (only the last marked position of a malformed stream can lie this close to the end)
+    label[k] = (int64_t)words[o + ALD_TS_GRAPH] + graph_offset;
+    sid[k] = o + ALD_TS_SID < n_words ? (int32_t)words[o + ALD_TS_SID] : 0;   // (only the last marked position of a malformed stream can lie this close to the end)
 }
 
 } // namespace

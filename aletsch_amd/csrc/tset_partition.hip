@@ -27,8 +27,8 @@ template<bool REC> __global__ void tp_owner(TpSrc s, int skip_single, uint32_t w
     const int64_t p = (int64_t)blockIdx.x * TX_BLOCK + threadIdx.x;
     if(p >= s.n) return;
     const uint32_t *r = s.base + s.off[p];
-    const int k = REC ? (int)r[REC_NEXW] : 2 * (int)r[5];
-    const int32_t *ex = REC ? rec_exons(r) : (const int32_t*)(r + ALD_TS_HDR);
+    const int k = REC ? (int)r[ALD_REC_NEXW] : 2 * (int)r[ALD_TS_NEXONS];
+    const int32_t *ex = REC ? rec_exons(r) : ts_exons(r);
     owner[p] = (uint32_t)(bucket_key_dev(ex, k) % world);
     ord[p] = (int32_t)p;
     len[p] = (k <= 2 && skip_single) ? 0 : ALD_TS_HDR + k;
@@ -56,15 +56,8 @@ template<bool REC> __global__ void tp_emit(TpSrc s, const int32_t *sord, const i
     const uint32_t *r = s.base + s.off[sord[i]];
     uint32_t *w = out + o;
     if(!REC) { for(int64_t q = l; q < n; q += 16) w[q] = r[q]; return; }
-    const int g = (int)r[0], k = (int)r[REC_NEXW];
-    if(l < ALD_TS_HDR) {
-        uint32_t v;
-        switch(l) { case 0: v = (uint32_t)g; break; case 1: v = r[1]; break; case 2: v = (uint32_t)(sid ? sid[g] : -1); break; case 3: v = r[5] & 0xFF; break; case 4: v = r[4]; break; case 5: v = (uint32_t)(k / 2); break;
-                    case 6: v = r[6]; break; case 7: v = r[7]; break;          /* weight */
-                    case 8: v = r[10]; break; case 9: v = r[11]; break;        /* conf   */
-                    case 10: v = r[8]; break; default: v = r[9]; break; }      /* abd    */
-        w[l] = v;
-    }
+    const int k = (int)r[ALD_REC_NEXW];
+    if(l < ALD_TS_HDR) w[l] = ts_header_word(r, l, sid);
     const uint32_t *x = (const uint32_t*)rec_exons(r);
     for(int q = l; q < k; q += 16) w[ALD_TS_HDR + q] = x[q];
 }

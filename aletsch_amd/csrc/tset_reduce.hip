@@ -40,17 +40,17 @@ __global__ void ix_order(const int32_t *n_paths, const int64_t *pbegin, const lo
 }
 __global__ void ix_widen(const int32_t *n_paths, int n, int64_t *len) { const int g = (int)((int64_t)blockIdx.x * TX_BLOCK + threadIdx.x); if(g <= n) len[g] = g < n ? (int64_t)n_paths[g] : 0; }
 
-// WEIGHT: also weight[p] = the record's weight (word 6), dense in (graph, path) order -- consecutive lanes write consecutive doubles -- for a
+// WEIGHT: also weight[p] = the record's weight (ALD_REC_WEIGHT), dense in (graph, path) order -- consecutive lanes write consecutive doubles -- for a
 // caller that has no host copy of the records and takes coverage = log(1 + weight) on the host (tx_front_coverage)
 template<bool WEIGHT> __global__ void tx_build(TxIn in, int32_t *nwords, uint64_t *key, int32_t *graph_of, double *weight)
 {
     const int64_t p = (int64_t)blockIdx.x * TX_BLOCK + threadIdx.x;
     if(p >= in.np) return;
     const uint32_t *r = in.pool + in.roff[p];
-    const int g = (int)r[0], k = (int)r[REC_NEXW]; const int strand = (int)(r[5] & 0xFF);
+    const int g = (int)r[ALD_REC_GRAPH], k = (int)r[ALD_REC_NEXW]; const int strand = (int)rec_strand(r);
     const int32_t *ex = rec_exons(r);
     nwords[p] = k; graph_of[p] = g;
-    if(WEIGHT) { double w; memcpy(&w, r + 6, 8); weight[p] = w; }
+    if(WEIGHT) { double w; memcpy(&w, r + ALD_REC_WEIGHT, 8); weight[p] = w; }
     if(k <= 2) { key[p] = TX_HOST; return; }
     const uint64_t bucket = chain_key_dev(ex, k);
     // group = (bucket, exons, strand, the words compare1 looks at: 1, 2 .. k-5, k-2); 32 bits of it ride in the sort key
@@ -68,9 +68,9 @@ template<bool WEIGHT> __global__ void tx_build(TxIn in, int32_t *nwords, uint64_
 __device__ inline bool same_group(const TxIn &in, int64_t a, int64_t b)
 {
     const uint32_t *ra = in.pool + in.roff[a], *rb = in.pool + in.roff[b];
-    const int ka = (int)ra[REC_NEXW], kb = (int)rb[REC_NEXW];
+    const int ka = (int)ra[ALD_REC_NEXW], kb = (int)rb[ALD_REC_NEXW];
     if(ka != kb) return false;
-    if((ra[5] & 0xFF) != (rb[5] & 0xFF)) return false;
+    if(rec_strand(ra) != rec_strand(rb)) return false;
     const int32_t *xa = rec_exons(ra), *xb = rec_exons(rb);
     if(xa[1] != xb[1] || xa[ka - 2] != xb[ka - 2]) return false;
     for(int q = 2; q + 5 <= ka; q++) if(xa[q] != xb[q]) return false;
@@ -91,22 +91,22 @@ __global__ void tx_fold(TxIn in, const uint64_t *skey, const int64_t *sidx, cons
     const int64_t i = (int64_t)blockIdx.x * TX_BLOCK + threadIdx.x;
     if(i >= n_dev || !head[i]) return;
     TxGroup G; G.first = sidx[i]; G.first_off = in.roff[sidx[i]]; G.bucket = (uint32_t)(skey[i] >> 32); G.count = 0; G.count1 = 0; G.coverage = 0; G.cov2 = 0; G.conf = 0; G.abd = 0; G.lo = 0; G.hi = 0; G.pad = 0;
-    { const uint32_t *r0 = in.pool + G.first_off; G.nw = (int32_t)r0[REC_NEXW]; G.graph = (int32_t)r0[0]; G.path = (int32_t)r0[1]; G.strand = (int32_t)(r0[5] & 0xFF); }
+    { const uint32_t *r0 = in.pool + G.first_off; G.nw = (int32_t)r0[ALD_REC_NEXW]; G.graph = (int32_t)r0[ALD_REC_GRAPH]; G.path = (int32_t)r0[ALD_REC_PATH]; G.strand = (int32_t)rec_strand(r0); }
     double inner = 0; int cur_g = -1; bool any = false;
     if(start_idx) { const int64_t z = start_idx[gid[i] - 1]; if(z >= 0) { G.coverage = start_cov[z]; any = true; } }
     for(int64_t m = i; m < n_dev && (m == i || !head[m]); m++) {
         const int64_t p = sidx[m]; const uint32_t *r = in.pool + in.roff[p];
-        const int g = (int)r[0]; const double c = cov[p];
-        double conf, abd; memcpy(&abd, r + 8, 8); memcpy(&conf, r + 10, 8);
-        const int32_t *x = rec_exons(r); const int k = (int)r[REC_NEXW];
+        const int g = (int)r[ALD_REC_GRAPH]; const double c = cov[p];
+        double conf, abd; memcpy(&abd, r + ALD_REC_ABD, 8); memcpy(&conf, r + ALD_REC_CONF, 8);
+        const int32_t *x = rec_exons(r); const int k = (int)r[ALD_REC_NEXW];
         if(g != cur_g) {                                 // the previous graph's own sum enters the set: moved in if the set had none, else added
             if(cur_g >= 0) { G.coverage = any ? G.coverage + inner : inner; any = true; }
             inner = c; cur_g = g;
         } else inner += c;                               // trans_item::merge inside the graph's own set (coverage adds for >= 2 exons)
-        if(m == i) { G.lo = x[0]; G.hi = x[k - 1]; G.cov2 = c; G.conf = conf; G.abd = abd; G.count1 = (int32_t)r[4]; }
+        if(m == i) { G.lo = x[0]; G.hi = x[k - 1]; G.cov2 = c; G.conf = conf; G.abd = abd; G.count1 = (int32_t)r[ALD_REC_COUNT]; }
         else {
             if(x[0] < G.lo) G.lo = x[0]; if(x[k - 1] > G.hi) G.hi = x[k - 1];
-            if(G.cov2 < c) G.cov2 = c; if(G.conf < conf) G.conf = conf; if(G.abd < abd) G.abd = abd; if(G.count1 < (int32_t)r[4]) G.count1 = (int32_t)r[4];
+            if(G.cov2 < c) G.cov2 = c; if(G.conf < conf) G.conf = conf; if(G.abd < abd) G.abd = abd; if(G.count1 < (int32_t)r[ALD_REC_COUNT]) G.count1 = (int32_t)r[ALD_REC_COUNT];
         }
         G.count++;
     }
@@ -134,9 +134,9 @@ __global__ void tx_sfold(TxIn in, const uint64_t *skey2, const int64_t *spos, co
     TxSample S; S.gid = (int32_t)(skey2[i] >> 32) - 1; S.sid = (int32_t)(uint32_t)(skey2[i] & 0xFFFFFFFFull) - 1; S.count1 = 0; S.pad = 0; S.cov2 = 0; S.conf = 0; S.abd = 0;
     for(int64_t m = i; m < n_dev && (m == i || !head2[m]); m++) {
         const int64_t p = sidx[spos[m]]; const uint32_t *r = in.pool + in.roff[p];
-        double conf, abd; memcpy(&abd, r + 8, 8); memcpy(&conf, r + 10, 8); const double c = cov[p];
-        if(m == i) { S.cov2 = c; S.conf = conf; S.abd = abd; S.count1 = (int32_t)r[4]; }
-        else { if(S.cov2 < c) S.cov2 = c; if(S.conf < conf) S.conf = conf; if(S.abd < abd) S.abd = abd; if(S.count1 < (int32_t)r[4]) S.count1 = (int32_t)r[4]; }
+        double conf, abd; memcpy(&abd, r + ALD_REC_ABD, 8); memcpy(&conf, r + ALD_REC_CONF, 8); const double c = cov[p];
+        if(m == i) { S.cov2 = c; S.conf = conf; S.abd = abd; S.count1 = (int32_t)r[ALD_REC_COUNT]; }
+        else { if(S.cov2 < c) S.cov2 = c; if(S.conf < conf) S.conf = conf; if(S.abd < abd) S.abd = abd; if(S.count1 < (int32_t)r[ALD_REC_COUNT]) S.count1 = (int32_t)r[ALD_REC_COUNT]; }
     }
     out[rid[i] - 1] = S;
 }
@@ -148,7 +148,7 @@ __global__ void ts_len(TxIn in, int skip_single, int64_t *len)
     const int64_t p = (int64_t)blockIdx.x * TX_BLOCK + threadIdx.x;
     if(p > in.np) return;
     if(p == in.np) { len[p] = 0; return; }                // (the exclusive scan over np + 1 entries leaves the total in the last one)
-    const int k = (int)in.pool[in.roff[p] + REC_NEXW];
+    const int k = (int)in.pool[in.roff[p] + ALD_REC_NEXW];
     len[p] = (k <= 2 && skip_single) ? 0 : (int64_t)ALD_TS_HDR + k;
 }
 // one 16-lane group per transcript: header by the first lanes, exon words copied with consecutive lanes on consecutive words
@@ -158,16 +158,9 @@ __global__ void ts_emit(TxIn in, const int64_t *at, const int32_t *sid, uint32_t
     if(p >= in.np) return;
     const int64_t o = at[p];
     if(at[p + 1] == o) return;
-    const uint32_t *r = in.pool + in.roff[p]; const int g = (int)r[0], k = (int)r[REC_NEXW];
+    const uint32_t *r = in.pool + in.roff[p]; const int k = (int)r[ALD_REC_NEXW];
     uint32_t *w = out + o;
-    if(l < ALD_TS_HDR) {
-        uint32_t v;
-        switch(l) { case 0: v = (uint32_t)g; break; case 1: v = r[1]; break; case 2: v = (uint32_t)(sid ? sid[g] : -1); break; case 3: v = r[5] & 0xFF; break; case 4: v = r[4]; break; case 5: v = (uint32_t)(k / 2); break;
-                    case 6: v = r[6]; break; case 7: v = r[7]; break;          /* weight */
-                    case 8: v = r[10]; break; case 9: v = r[11]; break;        /* conf   */
-                    case 10: v = r[8]; break; default: v = r[9]; break; }      /* abd    */
-        w[l] = v;
-    }
+    if(l < ALD_TS_HDR) w[l] = ts_header_word(r, l, sid);
     const uint32_t *x = (const uint32_t*)rec_exons(r);
     for(int q = l; q < k; q += 16) w[ALD_TS_HDR + q] = x[q];
 }
@@ -179,7 +172,7 @@ __global__ void sx_len(TxIn in, const int64_t *hp, int64_t ns, int64_t *len)
     if(a > ns) return;
     if(a == ns) { len[a] = 0; return; }                   // (the exclusive scan over ns + 1 entries leaves the total in the last one)
     const uint32_t *r = in.pool + in.roff[hp[a]];
-    len[a] = (int64_t)rec_words(r[2], r[REC_NEXW]);       // header + vertices + exon words, padded to even
+    len[a] = (int64_t)rec_words(r[ALD_REC_NV], r[ALD_REC_NEXW]);       // header + vertices + exon words, padded to even
 }
 // one 16-lane group per record, consecutive lanes on consecutive words (as ts_emit copies)
 __global__ void sx_copy(TxIn in, const int64_t *hp, const int64_t *at, int64_t ns, uint32_t *out)
@@ -345,15 +338,15 @@ void tx_host_singles(aletsch::transcript_sink &into, const std::vector<int64_t> 
     auto rec_at = [&](size_t a) { return h_off ? h_pool + h_off[a] : h_pool + h_roff[(size_t)host_paths[a]]; };
     auto fill = [&](size_t a) {
         const int64_t p = host_paths[a];
-        const uint32_t *r = rec_at(a); const int g = (int)r[0];
-        double conf, abd; memcpy(&abd, r + 8, 8); memcpy(&conf, r + 10, 8);
-        x.strand = (char)(r[5] & 0xFF); x.coverage = h_cov[(size_t)p]; x.top.cov2 = x.coverage; x.top.conf = conf; x.top.abd = abd; x.top.count1 = (int32_t)r[4]; x.count2 = 1;
-        x.tid = h_tid ? h_tid[(size_t)p] : tid_base + (((label ? label[g] : (int64_t)g) << 20) | (int64_t)r[1]);
-        const int32_t *ex = rec_exons(r); x.xs.assign(ex, ex + r[REC_NEXW]);
+        const uint32_t *r = rec_at(a); const int g = (int)r[ALD_REC_GRAPH];
+        const double abd = rec_f64(r, ALD_REC_ABD), conf = rec_f64(r, ALD_REC_CONF);
+        x.strand = (char)rec_strand(r); x.coverage = h_cov[(size_t)p]; x.top.cov2 = x.coverage; x.top.conf = conf; x.top.abd = abd; x.top.count1 = (int32_t)r[ALD_REC_COUNT]; x.count2 = 1;
+        x.tid = h_tid ? h_tid[(size_t)p] : tid_base + (((label ? label[g] : (int64_t)g) << 20) | (int64_t)r[ALD_REC_PATH]);
+        const int32_t *ex = rec_exons(r); x.xs.assign(ex, ex + r[ALD_REC_NEXW]);
     };
     for(size_t a = 0; a < host_paths.size(); ) {          // one per-graph set per graph that has any (assembler.cc:1105-1133)
-        const int g = (int)rec_at(a)[0];
-        size_t e = a; while(e < host_paths.size() && (int)rec_at(e)[0] == g) e++;
+        const int g = (int)rec_at(a)[ALD_REC_GRAPH];
+        size_t e = a; while(e < host_paths.size() && (int)rec_at(e)[ALD_REC_GRAPH] == g) e++;
         if(e - a == 1) { fill(a); into.add(x, 1, sid ? sid[g] : -1); }   // merging a one-item set is the same as adding the item (transcript_set.cc:149-175)
         else {
             aletsch::transcript_sink ts(into.single_exon_overlap());
@@ -372,16 +365,16 @@ int tx_stream_records(const uint32_t *words, int64_t n_words, const double *cove
     int64_t ti = -1;                                       // ti: ordinal of the transcript in the stream (index into `coverage`)
     const int rc = tx_walk_stream(words, n_words, [&](int64_t o, bool first) {
         ti++;
-        const int64_t k = 2 * (int64_t)words[o + 5];
-        if(first) { label.push_back((int64_t)words[o] + graph_offset); sid.push_back((int32_t)words[o + 2]); }
+        const uint32_t *w = words + o; const int64_t k = ts_nexw(w);
+        if(first) { label.push_back((int64_t)w[ALD_TS_GRAPH] + graph_offset); sid.push_back((int32_t)w[ALD_TS_SID]); }
         if(skip_single_exon && k <= 2) return;
         const size_t at = pool.size(); roff.push_back((unsigned long long)at);
         pool.resize(at + (size_t)rec_words(2, (unsigned)k), 0);
         uint32_t *r = pool.data() + at;
-        r[0] = (uint32_t)(label.size() - 1); r[1] = words[o + 1]; r[2] = 2; r[3] = 0; r[4] = words[o + 4]; r[5] = words[o + 3] & 0xFF;
-        r[6] = words[o + 6]; r[7] = words[o + 7]; r[8] = words[o + 10]; r[9] = words[o + 11]; r[10] = words[o + 8]; r[11] = words[o + 9]; r[12] = r[13] = 0; r[REC_NEXW] = (uint32_t)k; r[REC_NEXW + 1] = 0;
-        memcpy(r + REC_HDR_WORDS + 2, words + o + ALD_TS_HDR, 4 * (size_t)k);
-        double w; memcpy(&w, words + o + 6, 8); cov.push_back(coverage ? coverage[ti] : log(1.0 + w)); if(tid) tids.push_back(tid[ti]);
+        const int32_t gid1 = (int32_t)label.size();
+        for(int l = 0; l < ALD_REC_HDR; l++) r[l] = rec_header_word_of_ts(w, l, &gid1);
+        memcpy(r + ALD_REC_HDR + 2, ts_exons(w), 4 * (size_t)k);
+        cov.push_back(coverage ? coverage[ti] : log(1.0 + ts_f64(w, ALD_TS_WEIGHT))); if(tid) tids.push_back(tid[ti]);
     });
     if(rc != ALD_OK) return rc;
     R.n_transcripts = ti + 1;

@@ -75,7 +75,7 @@ __device__ inline int cmp1(int na, int sa, const int32_t *xa, int nb, int sb, co
     if(xa[na - 2] != xb[na - 2]) return xa[na - 2] < xb[na - 2] ? 1 : -1;
     return 0;
 }
-__device__ inline int rec_strand(const uint32_t *r) { return (int)(int8_t)(r[5] & 0xFF); }      // the reference's `char` strand
+__device__ inline int rec_strand_char(const uint32_t *r) { return (int)(int8_t)rec_strand(r); }      // the reference's `char` strand
 
 // The incoming side of a merge, two kinds with one interface.  j: position in (hash, compare1) order.
 struct InBatch {                     // a batch's groups: before the fold only hash / nw / strand / x are valid (they come from the records)
@@ -84,8 +84,8 @@ struct InBatch {                     // a batch's groups: before the fold only h
     int64_t tid_base; const int64_t *label, *ptid; int64_t n;
     __device__ const uint32_t *rec(int64_t j) const { return in.pool + in.roff[sidx[ghead[perm[j]]]]; }
     __device__ uint64_t hash(int64_t j) const { return skey[ghead[perm[j]]] >> 32; }
-    __device__ int nw(int64_t j) const { return (int)rec(j)[REC_NEXW]; }
-    __device__ int strand(int64_t j) const { return rec_strand(rec(j)); }
+    __device__ int nw(int64_t j) const { return (int)rec(j)[ALD_REC_NEXW]; }
+    __device__ int strand(int64_t j) const { return rec_strand_char(rec(j)); }
     __device__ const int32_t *x(int64_t j) const { return rec_exons(rec(j)); }
     __device__ int32_t lo(int64_t j) const { return grp[perm[j]].lo; }
     __device__ int32_t hi(int64_t j) const { return grp[perm[j]].hi; }
@@ -130,7 +130,7 @@ __global__ void sr_len(const uint32_t *words, const unsigned long long *toff, in
     const int64_t i = lane_id();
     if(i > nt) return;
     if(i == nt) { len[i] = 0; keep[i] = 0; return; }        // (the exclusive scans over nt + 1 entries leave the totals in the last one)
-    const int64_t k = 2 * (int64_t)words[toff[i] + 5];
+    const int64_t k = 2 * (int64_t)words[toff[i] + ALD_TS_NEXONS];
     const bool kp = !(skip_single && k <= 2);
     len[i] = kp ? (int64_t)rec_words(2, (unsigned)k) : 0; keep[i] = kp ? 1 : 0;
 }
@@ -143,16 +143,10 @@ __global__ void sr_emit(const uint32_t *words, const unsigned long long *toff, c
     const int64_t o = at[i];
     if(at[i + 1] == o) return;
     const uint32_t *w = words + toff[i]; uint32_t *r = pool + o;
-    const int k = 2 * (int)w[5];
-    uint32_t v;
-    switch(l) { case 0: v = (uint32_t)(gid[i] - 1); break; case 1: v = w[1]; break; case 2: v = 2; break; case 4: v = w[4]; break; case 5: v = w[3] & 0xFF; break;
-                case 6: v = w[6]; break; case 7: v = w[7]; break;          /* weight */
-                case 8: v = w[10]; break; case 9: v = w[11]; break;        /* abd    */
-                case 10: v = w[8]; break; case 11: v = w[9]; break;        /* conf   */
-                case REC_NEXW: v = (uint32_t)k; break; default: v = 0; break; }
-    r[l] = v;
-    if(l < 2) r[REC_HDR_WORDS + l] = 0;
-    for(int q = l; q < k; q += 16) r[REC_HDR_WORDS + 2 + q] = w[ALD_TS_HDR + q];
+    const int k = 2 * (int)w[ALD_TS_NEXONS];
+    r[l] = rec_header_word_of_ts(w, l, gid + i);
+    if(l < 2) r[ALD_REC_HDR + l] = 0;
+    for(int q = l; q < k; q += 16) r[ALD_REC_HDR + 2 + q] = w[ALD_TS_HDR + q];
     if(l == 0) { const int32_t p = kord[i]; roff[p] = (unsigned long long)o; if(cov_in) cov[p] = cov_in[i]; if(tid_in) tid[p] = tid_in[i]; }
 }
 
@@ -177,7 +171,7 @@ __global__ void rs_order(TxIn in, const int64_t *sidx, const int32_t *ghead, con
         int64_t p = q;
         while(p > k) {
             const uint32_t *ru = in.pool + in.roff[sidx[ghead[perm[p - 1]]]];
-            if(cmp1((int)rv[REC_NEXW], rec_strand(rv), rec_exons(rv), (int)ru[REC_NEXW], rec_strand(ru), rec_exons(ru)) != 1) break;
+            if(cmp1((int)rv[ALD_REC_NEXW], rec_strand_char(rv), rec_exons(rv), (int)ru[ALD_REC_NEXW], rec_strand_char(ru), rec_exons(ru)) != 1) break;
             perm[p] = perm[p - 1]; p--;
         }
         perm[p] = v;
@@ -442,10 +436,10 @@ int add_device_stream(ald_tset_dev *s, const uint32_t *d_words, int64_t n_words,
     s->st_transcripts = nt; s->st_groups = ng;
     StreamRecScratch &R = s->sr;
     DevBuf &d_len = R.len, &d_at = R.at, &d_keep = R.keep, &d_kord = R.kord, &d_tmp = R.cub_tmp, &d_covin = R.cov_in, &d_tidin = R.tid_in, &d_cov = R.cov, &d_tidk = R.tid;
-    // a scratch record has 6 words more than its transcript has in the stream (18 + k against 12 + k)
+    // a scratch record has 6 words more than its transcript has in the stream (ALD_REC_HDR + 2 + k against ALD_TS_HDR + k)
     if(d_len.ensure(8 * (size_t)(nt + 1)) || d_at.ensure(8 * (size_t)(nt + 1)) || d_keep.ensure(4 * (size_t)(nt + 1)) || d_kord.ensure(4 * (size_t)(nt + 1))
        || (coverage && (d_covin.ensure(8 * (size_t)nt) || d_cov.ensure(8 * (size_t)nt))) || (tid && (d_tidin.ensure(8 * (size_t)nt) || d_tidk.ensure(8 * (size_t)nt)))
-       || s->d_pool.ensure(4 * (size_t)(n_words + 6 * nt) + 64) || s->d_roff.ensure(8 * (size_t)nt + 8) || R.p_head.ensure(16 + 12 * (size_t)ng + 64)) return ald_set_err(ALD_ERR_NOMEM, "resident set stream buffers");
+       || s->d_pool.ensure(4 * (size_t)(n_words + (ALD_REC_HDR + 2 - ALD_TS_HDR) * nt) + 64) || s->d_roff.ensure(8 * (size_t)nt + 8) || R.p_head.ensure(16 + 12 * (size_t)ng + 64)) return ald_set_err(ALD_ERR_NOMEM, "resident set stream buffers");
     if(coverage) HCHK(hipMemcpyAsync(d_covin.p, coverage, 8 * (size_t)nt, hipMemcpyHostToDevice, st));
     if(tid) HCHK(hipMemcpyAsync(d_tidin.p, tid, 8 * (size_t)nt, hipMemcpyHostToDevice, st));
     hipLaunchKernelGGL(sr_len, dim3(grid_for(nt + 1)), dim3(TX_BLOCK), 0, st, d_words, I.toff, nt, (int)(skip_single_exon != 0), (int64_t*)d_len.p, (int32_t*)d_keep.p);

@@ -12,7 +12,13 @@ import numpy as np
 import torch
 import torch.distributed as dist
 
-REC_HDR_WORDS = 16          # decomp_common.h: record header words ([14] = number of exon words behind the vertices)
+# Word indices of a path record and of a transcript-stream record: the ALD_REC_* / ALD_TS_* enums of include/aletsch_decomp.h (an f64
+# takes two words).  The two formats hold conf and abd in opposite order.
+(ALD_REC_GRAPH, ALD_REC_PATH, ALD_REC_NV, ALD_REC_LENGTH, ALD_REC_COUNT, ALD_REC_STRAND, ALD_REC_WEIGHT, ALD_REC_ABD, ALD_REC_CONF,
+ ALD_REC_READS, ALD_REC_NEXW, ALD_REC_HDR) = 0, 1, 2, 3, 4, 5, 6, 8, 10, 12, 14, 16
+(ALD_TS_GRAPH, ALD_TS_PATH, ALD_TS_SID, ALD_TS_STRAND, ALD_TS_COUNT1, ALD_TS_NEXONS, ALD_TS_WEIGHT, ALD_TS_CONF, ALD_TS_ABD,
+ ALD_TS_HDR) = 0, 1, 2, 3, 4, 5, 6, 8, 10, 12
+REC_HDR_WORDS = ALD_REC_HDR
 
 
 def shard_range(n_graphs: int, rank: int, world: int):
@@ -161,14 +167,15 @@ def gather_records(rec, device: torch.device, graph_offset: int = 0):
 def parse_records(words: np.ndarray):
     """Decode a record stream into a list of dicts sorted by (graph, path index)."""
     out = []; o = 0
-    while o + REC_HDR_WORDS <= words.size:
-        nv = int(words[o + 2]); nx = int(words[o + 14])
-        f = words[o + 6:o + 14].view(np.float64)
-        out.append(dict(graph=int(words[o]), index=int(words[o + 1]), length=int(words[o + 3]), count=int(words[o + 4]),
-                        strand=chr(int(words[o + 5]) & 0xFF), attempt=(int(words[o + 5]) >> 8) & 0xFF,
-                        weight=float(f[0]), abd=float(f[1]), conf=float(f[2]), reads=float(f[3]),
-                        v=words[o + REC_HDR_WORDS:o + REC_HDR_WORDS + nv].astype(np.int32).tolist(),
-                        exons=words[o + REC_HDR_WORDS + nv:o + REC_HDR_WORDS + nv + nx].astype(np.int32).reshape(-1, 2).tolist()))
-        w = REC_HDR_WORDS + nv + nx; o += w + (w & 1)
+    while o + ALD_REC_HDR <= words.size:
+        r = words[o:]
+        nv = int(r[ALD_REC_NV]); nx = int(r[ALD_REC_NEXW])
+        f64 = lambda word: float(r[word:word + 2].view(np.float64)[0])
+        out.append(dict(graph=int(r[ALD_REC_GRAPH]), index=int(r[ALD_REC_PATH]), length=int(r[ALD_REC_LENGTH]), count=int(r[ALD_REC_COUNT]),
+                        strand=chr(int(r[ALD_REC_STRAND]) & 0xFF), attempt=(int(r[ALD_REC_STRAND]) >> 8) & 0xFF,
+                        weight=f64(ALD_REC_WEIGHT), abd=f64(ALD_REC_ABD), conf=f64(ALD_REC_CONF), reads=f64(ALD_REC_READS),
+                        v=r[ALD_REC_HDR:ALD_REC_HDR + nv].astype(np.int32).tolist(),
+                        exons=r[ALD_REC_HDR + nv:ALD_REC_HDR + nv + nx].astype(np.int32).reshape(-1, 2).tolist()))
+        w = ALD_REC_HDR + nv + nx; o += w + (w & 1)
     out.sort(key=lambda r: (r["graph"], r["index"]))
     return out

@@ -345,6 +345,10 @@ int  ald_tset_add_batch(ald_tset *t, const ald_batch *b, const int32_t *sid, int
  * Only graphs that ended ALD_ST_OK / ALD_ST_SKIPPED_LARGE contribute, records of abandoned capacity attempts are gone, exons are joined,
  * single-exon transcripts are left out when skip_single_exon (assembler.cc:1117).  Valid until the next call on this batch. */
 int  ald_batch_transcript_stream(const ald_batch *b, const int32_t *sid, int32_t skip_single_exon, const uint32_t **words, int64_t *n_words);
+/* word indices of the header above (an f64 takes two words); the exons begin at ALD_TS_HDR.  NOTE conf before abd: the path record below
+ * (ALD_REC_*) has abd before conf. */
+enum { ALD_TS_GRAPH = 0, ALD_TS_PATH = 1, ALD_TS_SID = 2, ALD_TS_STRAND = 3, ALD_TS_COUNT1 = 4, ALD_TS_NEXONS = 5,
+       ALD_TS_WEIGHT = 6, ALD_TS_CONF = 8, ALD_TS_ABD = 10, ALD_TS_HDR = 12 };
 /* The same stream, word for word, built by kernels and left in DEVICE memory (exon join, lengths, prefix sum, fill): for the RCCL
  * exchange of a multi-process host (ald_comm_gather_streams takes host or device pointers alike; torch.distributed a zero-copy view),
  * so that the finished transcripts travel HBM -> xGMI -> HBM of rank 0 without a detour through this rank's host memory.
@@ -499,6 +503,10 @@ int  ald_records_add_graph_offset(uint32_t *words, int64_t n_words, int32_t grap
  * rnacore/essential.cc:735-746 done by the kernel).  The pool also holds the records of abandoned capacity attempts; the records that
  * count are the ones the index names. */
 int  ald_batch_raw_records(const ald_batch *b, const uint32_t **words, int64_t *n_words);
+/* word indices of the header above (an f64 takes two words); the vertices begin at ALD_REC_HDR, the exon words follow them.  NOTE abd
+ * before conf: the transcript stream (ALD_TS_*) has conf before abd. */
+enum { ALD_REC_GRAPH = 0, ALD_REC_PATH = 1, ALD_REC_NV = 2, ALD_REC_LENGTH = 3, ALD_REC_COUNT = 4, ALD_REC_STRAND = 5 /* | attempt << 8 */,
+       ALD_REC_WEIGHT = 6, ALD_REC_ABD = 8, ALD_REC_CONF = 10, ALD_REC_READS = 12, ALD_REC_NEXW = 14, ALD_REC_HDR = 16 };
 /* the result index the decomposition kernel wrote (replaces walking sx.paths / sx.trsts, scallop.h:50-51): index[graph_first[g] + p] =
  * word offset of record (g, p) in the pool above, p < num_paths of g; graph_first[g] = -1 for a graph without paths or one that did
  * not end well.  Host copies of the last download, valid until the next one. */

@@ -38,8 +38,8 @@ int femur_features(HostBatch *Bp, const int64_t *path_offset, const int64_t *pv_
             pool.resize(pool.size() + 5, 0xDEADBEEFu);
             index[(size_t)p] = pool.size();
             const int k = (int)(pv_offset[p + 1] - pv_offset[p]);
-            uint32_t hdr[REC_HDR_WORDS] = {0}; hdr[0] = (uint32_t)g; hdr[1] = (uint32_t)(p - path_offset[g]); hdr[2] = (uint32_t)k;
-            pool.insert(pool.end(), hdr, hdr + REC_HDR_WORDS);
+            uint32_t hdr[ALD_REC_HDR] = {0}; hdr[ALD_REC_GRAPH] = (uint32_t)g; hdr[ALD_REC_PATH] = (uint32_t)(p - path_offset[g]); hdr[ALD_REC_NV] = (uint32_t)k;
+            pool.insert(pool.end(), hdr, hdr + ALD_REC_HDR);
             for(int i = 0; i < k; i++) pool.push_back((uint32_t)path_vertices[pv_offset[p] + i]);
         }
     }

@@ -53,7 +53,7 @@ static int emu_run_batch(HostBatch &B, const ald_params *prm, int32_t trace_cap,
     if(const char *ev = getenv("ALD_DEBUG_POOL_WORDS")) { const long long k = atoll(ev); if(k > 0 && (uint64_t)k < pool_cap) pool_cap = (uint64_t)k; }     // same knob as ald_batch_upload
     std::vector<uint32_t> pool(pool_cap); unsigned long long counters[2] = {0, 0};      // [0] pool words used, [1] index entries used (as in the batch's counter buffer)
     unsigned long long &pool_used = counters[0], &index_used = counters[1];
-    uint64_t index_cap = pool_cap / (REC_HDR_WORDS + 2) + 1;
+    uint64_t index_cap = pool_cap / (ALD_REC_HDR + 2) + 1;
     std::vector<unsigned long long> index(index_cap); std::vector<long long> graph_first(n, -1);
     emu_result *E = new emu_result(); E->n = n; E->trace_cap = trace_cap;
     if(trace_cap > 0) { E->trace_n.assign(n, 0); E->trace_codes.assign(3ull * n * trace_cap, 0); E->trace_vals.assign((size_t)n * trace_cap, 0); }
@@ -100,7 +100,7 @@ static int emu_run_batch(HostBatch &B, const ald_params *prm, int32_t trace_cap,
     if(!pool_full || regrow >= 8) break;
     pool_cap = std::max<uint64_t>(2 * pool_cap, pool_used + pool_used / 4 + 4096); pool.assign(pool_cap, 0);
     A.out.pool = pool.data(); A.out.pool_cap = pool_cap;
-    index_cap = pool_cap / (REC_HDR_WORDS + 2) + 1; index.assign(index_cap, 0); A.out.index = index.data(); A.out.index_cap = index_cap;
+    index_cap = pool_cap / (ALD_REC_HDR + 2) + 1; index.assign(index_cap, 0); A.out.index = index.data(); A.out.index_cap = index_cap;
   }
     E->R.status = status; E->R.n_iters = n_iters;
     E->R.pool.assign(pool.begin(), pool.begin() + std::min<uint64_t>(pool_used, pool_cap));
