@@ -1,17 +1,21 @@
 // Driver (ours) over the REFERENCE's transcript_set (rnacore/transcript_set.cc + gtf/transcript.cc), compiled against
 // /root/reference sources.  It replays what assembler::assemble(gx, px, sid) does with the transcripts of each graph
 // (meta/assembler.cc:1105-1133): per graph a local set `ts`, ts.add(t, 1, sid, ADD) for every transcript, then tm.add(ts, ADD).
+// With the arguments `merge K1 K2 ...` (K1 + K2 + ... = G) the groups are cut into consecutive segments of K1, K2, ... groups, every
+// segment is replayed into a transcript_set of its own, and the sets are folded left to right into the first with
+// transcript_set::add(transcript_set&, TRANSCRIPT_COUNT_ADD_COVERAGE_ADD): two finished sets that both hold items.  The first set is printed.
 // stdin:  G  then per graph "sid n" and n lines "strand coverage conf abd count1 nexons l r ... tid"
 // stdout: every item of tm in map order:  hash count coverage cov2 conf abd count1 count2 tid nexons l r ... | nsamples {sid coverage cov2 conf abd count1 count2}
 #include "transcript_set.h"
 #include "constants.h"
 #include <cstdio>
+#include <cstdlib>
+#include <cstring>
 #include <string>
-int main()
+#include <vector>
+// one region replayed into tm: G groups read from stdin
+static int replay(transcript_set &tm, int G)
 {
-	int G;
-	if(scanf("%d", &G) != 1) return 1;
-	transcript_set tm("1", 0, 0.8);
 	for(int g = 0; g < G; g++)
 	{
 		int sid, n;
@@ -31,6 +35,29 @@ int main()
 		}
 		tm.add(ts, TRANSCRIPT_COUNT_ADD_COVERAGE_ADD);
 	}
+	return 0;
+}
+int main(int argc, char **argv)
+{
+	int G;
+	if(scanf("%d", &G) != 1) return 1;
+	std::vector<int> seg;
+	if(argc >= 2)
+	{
+		if(strcmp(argv[1], "merge") != 0 || argc < 3) return 2;
+		long sum = 0;
+		for(int a = 2; a < argc; a++) { int k = atoi(argv[a]); if(k < 0) return 2; seg.push_back(k); sum += k; }
+		if(sum != G) return 2;
+	}
+	else seg.push_back(G);
+	std::vector<transcript_set> sets;
+	for(size_t s = 0; s < seg.size(); s++)
+	{
+		sets.push_back(transcript_set("1", 0, 0.8));
+		if(replay(sets.back(), seg[s]) != 0) return 1;
+	}
+	transcript_set &tm = sets[0];
+	for(size_t s = 1; s < sets.size(); s++) tm.add(sets[s], TRANSCRIPT_COUNT_ADD_COVERAGE_ADD);
 	for(auto &x : tm.mt) for(auto &z : x.second)
 	{
 		const transcript &t = z.trst;
