@@ -947,7 +947,7 @@ int ald_tset_add_batch(ald_tset *t, const ald_batch *b, const int32_t *sid, int6
     merge_groups(t, nthr, n, b->res.path_begin.data(), sid, bucket.data(), [&](int64_t i, aletsch::sink_transcript &x) {
         const PathRec p = b->res.path((int64_t)((size_t)i));
         x.strand = p.strand; x.coverage = p.coverage; x.top.cov2 = x.coverage; x.top.conf = p.conf; x.top.abd = p.abd; x.top.count1 = p.count; x.count2 = 1;
-        x.tid = tid_base + (((int64_t)p.graph << 20) | (int64_t)p.index);
+        x.tid = transcript_tid(tid_base, (int64_t)p.graph, (int64_t)p.index);
         const int32_t *ex = b->res.exons(p);
         x.xs.assign(ex, ex + p.nexw);
     }, [&](int64_t i) { __builtin_prefetch(b->res.rec(i)); __builtin_prefetch(b->res.rec(i) + 16); });
@@ -1003,7 +1003,7 @@ int ald_tset_add_stream(ald_tset *t, const uint32_t *words, int64_t n_words, int
     merge_groups(t, nthr, (int64_t)grp_sid.size(), grp.data(), grp_sid.data(), bucket.data(), [&](int64_t i, aletsch::sink_transcript &x) {
         const uint32_t *w = words + offs[(size_t)i];
         x.strand = (char)w[ALD_TS_STRAND]; x.coverage = log(1.0 + ts_f64(w, ALD_TS_WEIGHT)); x.top.cov2 = x.coverage; x.top.conf = ts_f64(w, ALD_TS_CONF); x.top.abd = ts_f64(w, ALD_TS_ABD); x.top.count1 = (int32_t)w[ALD_TS_COUNT1]; x.count2 = 1;
-        x.tid = tid_base + ((((int64_t)w[ALD_TS_GRAPH] + graph_offset) << 20) | (int64_t)w[ALD_TS_PATH]);
+        x.tid = transcript_tid(tid_base, (int64_t)w[ALD_TS_GRAPH] + graph_offset, (int64_t)w[ALD_TS_PATH]);
         x.xs.assign(ts_exons(w), ts_exons(w) + ts_nexw(w));
     }, [&](int64_t i) { const uint32_t *w = words + offs[(size_t)i]; __builtin_prefetch(w); __builtin_prefetch((const char*)w + 64); });
     if(getenv("ALD_SINK_PROF")) { const auto T3 = std::chrono::steady_clock::now(); auto ms = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point c) { return std::chrono::duration<double, std::milli>(c - a).count(); };
@@ -1031,19 +1031,12 @@ int ald_tset_export(const ald_tset *t, uint64_t *hash, int32_t *count, char *str
                     int32_t *count1, int32_t *count2, int64_t *tid, int64_t *exon_offset, int32_t *exon_lr,
                     int64_t *sample_offset, int32_t *sample_sid, double *sample_cov2, double *sample_conf, double *sample_abd, int32_t *sample_count1)
 {
-    if(!t || !hash || !count || !strand || !coverage || !cov2 || !conf || !abd || !count1 || !count2 || !tid || !exon_offset || !exon_lr || !sample_offset || !sample_sid || !sample_cov2 || !sample_conf || !sample_abd || !sample_count1) return ALD_ERR_INVALID;
-    int64_t i = 0, e = 0, s = 0;
-    std::vector<size_t> keys; for(auto &sh : t->shard) for(auto &x : sh.mt) keys.push_back(x.first);
-    std::sort(keys.begin(), keys.end());
-    for(size_t key : keys) for(auto &z : t->shard[key % ALD_TSET_SHARDS].mt.find(key)->second) {        // the reference's iteration order: ascending hash
-        const aletsch::sink_transcript &r = z.trst;
-        hash[i] = (uint64_t)key; count[i] = z.count; strand[i] = r.strand; coverage[i] = r.coverage; cov2[i] = r.top.cov2; conf[i] = r.top.conf; abd[i] = r.top.abd;
-        count1[i] = r.top.count1; count2[i] = r.count2; tid[i] = r.tid; exon_offset[i] = e; sample_offset[i] = s;
-        memcpy(exon_lr + 2 * e, r.xs.data(), 4 * r.xs.size()); e += (int64_t)r.n_exons();
-        for(auto &q : z.samples) { sample_sid[s] = q.first; sample_cov2[s] = q.second.top.cov2; sample_conf[s] = q.second.top.conf; sample_abd[s] = q.second.top.abd; sample_count1[s] = q.second.top.count1; s++; }
-        i++;
-    }
-    exon_offset[i] = e; sample_offset[i] = s;
+    if(!t) return ALD_ERR_INVALID;
+    const SinkRows rows = sink_rows(t->shard.data(), t->shard.size());                                  // the reference's iteration order: ascending hash
+    const FlatMut out{hash, count, strand, coverage, cov2, conf, abd, count1, count2, tid, exon_offset, exon_lr, sample_offset, sample_sid, sample_cov2, sample_conf, sample_abd, sample_count1, (int64_t)rows.item.size(), rows.ne, rows.ns};
+    if(flat_has_null(out)) return ALD_ERR_INVALID;
+    exon_offset[0] = sample_offset[0] = 0;
+    for(int64_t i = 0; i < out.n; i++) flat_put_item(out, i, rows.hash[(size_t)i], *rows.item[(size_t)i]);
     return ALD_OK;
 }
 

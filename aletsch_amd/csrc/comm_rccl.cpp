@@ -235,13 +235,6 @@ static int grouped(ald_comm *c, ncclDataType_t type, const std::vector<Xfer> &se
     return ALD_OK;
 }
 
-static bool in_device_memory(const void *p)
-{
-    hipPointerAttribute_t at; const bool dev = p && hipPointerGetAttributes(&at, p) == hipSuccess && at.type == hipMemoryTypeDevice;
-    (void)hipGetLastError();                                   // (a plain host pointer makes the query fail: not an error here)
-    return dev;
-}
-
 int ald_comm_exchange_streams(ald_comm *c, const uint32_t *words, const int64_t *offsets, int32_t graph_offset,
                               const uint32_t **dev_words, const int64_t **seg_offsets, const int32_t **graph_offsets)
 {
@@ -260,7 +253,7 @@ int ald_comm_exchange_streams(ald_comm *c, const uint32_t *words, const int64_t 
     for(int q = 0; q < W; q++) { c->x_seg[(size_t)q + 1] = c->x_seg[(size_t)q] + count(q, c->rank); c->x_goffs[(size_t)q] = (int32_t)all[(size_t)q * (size_t)(W + 1) + (size_t)W]; }
     // sub-streams that already live in HBM are sent from where they are; host memory is staged first
     const uint32_t *src = words; const int64_t n_mine = offsets[W] - offsets[0];
-    if(n_mine > 0 && !in_device_memory(words)) {
+    if(n_mine > 0 && !tx_on_device(words)) {
         if(c->d_send.ensure(4 * (size_t)n_mine + 64)) return ald_set_err(ALD_ERR_NOMEM, "send buffer");
         HCHK(hipMemcpyAsync(c->d_send.p, words + offsets[0], 4 * (size_t)n_mine, hipMemcpyHostToDevice, c->stream));
         src = (const uint32_t*)c->d_send.p - offsets[0];
@@ -278,46 +271,6 @@ int ald_comm_exchange_streams(ald_comm *c, const uint32_t *words, const int64_t 
     return ALD_OK;
 }
 
-} // extern "C"
-
-/* a flat set as ONE run of 8-byte words: n, exons, samples, then every array, each padded to a multiple of 8 bytes */
-namespace {
-template<class V> void put(std::vector<uint64_t> &buf, const V &v, size_t n)
-{
-    const size_t bytes = n * sizeof(v[0]), at = buf.size();
-    buf.resize(at + (bytes + 7) / 8, 0);
-    if(bytes) memcpy(buf.data() + at, v.data(), bytes);
-}
-template<class T> const T *take(const uint64_t *&p, size_t n) { const T *r = (const T*)p; p += (n * sizeof(T) + 7) / 8; return r; }
-struct FlatView {
-    int64_t n, ne, ns; const uint64_t *hash; const int32_t *count, *count1, *count2; const char *strand; const double *coverage, *cov2, *conf, *abd; const int64_t *tid, *exon_offset, *sample_offset;
-    const int32_t *exon_lr, *sample_sid, *sample_count1; const double *sample_cov2, *sample_conf, *sample_abd;
-};
-void pack(const ald_tset_flat &f, std::vector<uint64_t> &buf)
-{
-    const size_t n = f.hash.size(), ne = f.exon_lr.size() / 2, ns = f.sample_sid.size();
-    buf.assign({(uint64_t)n, (uint64_t)ne, (uint64_t)ns});
-    put(buf, f.hash, n); put(buf, f.count, n); put(buf, f.count1, n); put(buf, f.count2, n); put(buf, f.strand, n); put(buf, f.coverage, n); put(buf, f.cov2, n); put(buf, f.conf, n); put(buf, f.abd, n);
-    put(buf, f.tid, n); put(buf, f.exon_offset, n + 1); put(buf, f.sample_offset, n + 1); put(buf, f.exon_lr, 2 * ne); put(buf, f.sample_sid, ns); put(buf, f.sample_count1, ns);
-    put(buf, f.sample_cov2, ns); put(buf, f.sample_conf, ns); put(buf, f.sample_abd, ns);
-}
-bool unpack(const uint64_t *p, int64_t words, FlatView &v)
-{
-    if(words < 3) return false;
-    const uint64_t *end = p + words;
-    v.n = (int64_t)p[0]; v.ne = (int64_t)p[1]; v.ns = (int64_t)p[2]; p += 3;
-    if(v.n < 0 || v.ne < 0 || v.ns < 0 || v.n > words || v.ne > words || v.ns > words) return false;
-    const size_t n = (size_t)v.n, ne = (size_t)v.ne, ns = (size_t)v.ns;
-    v.hash = take<uint64_t>(p, n); v.count = take<int32_t>(p, n); v.count1 = take<int32_t>(p, n); v.count2 = take<int32_t>(p, n); v.strand = take<char>(p, n);
-    v.coverage = take<double>(p, n); v.cov2 = take<double>(p, n); v.conf = take<double>(p, n); v.abd = take<double>(p, n); v.tid = take<int64_t>(p, n);
-    v.exon_offset = take<int64_t>(p, n + 1); v.sample_offset = take<int64_t>(p, n + 1); v.exon_lr = take<int32_t>(p, 2 * ne); v.sample_sid = take<int32_t>(p, ns); v.sample_count1 = take<int32_t>(p, ns);
-    v.sample_cov2 = take<double>(p, ns); v.sample_conf = take<double>(p, ns); v.sample_abd = take<double>(p, ns);
-    return p == end && v.exon_offset[n] == v.ne && v.sample_offset[n] == v.ns;
-}
-} // namespace
-
-extern "C" {
-
 int ald_comm_gather_sets(ald_comm *c, const ald_tset_flat *f, ald_tset_flat **out)
 {
     if(!c || !f || !out) return ALD_ERR_INVALID;
@@ -328,7 +281,7 @@ int ald_comm_gather_sets(ald_comm *c, const ald_tset_flat *f, ald_tset_flat **ou
     bool foreign = false;
     for(size_t i = 0; i < f->hash.size() && !foreign; i++) foreign = (int)(f->hash[i] % (uint64_t)W) != c->rank;
     std::vector<uint64_t> buf;
-    if(!foreign) pack(*f, buf);
+    if(!foreign) flat_pack(flat_view(*f), buf);                // (the wire form: tset_flat.h)
     int64_t mine = foreign ? -1 : (int64_t)buf.size();
     std::vector<int64_t> all;
     { int rc = exchange_sizes(c, &mine, 1, all); if(rc != ALD_OK) return rc; }
@@ -344,35 +297,23 @@ int ald_comm_gather_sets(ald_comm *c, const ald_tset_flat *f, ald_tset_flat **ou
     if(c->rank != 0) return ALD_OK;
     std::vector<uint64_t> got((size_t)at[(size_t)W]);
     HCHK(hipMemcpy(got.data(), c->d_xrecv.p, 8 * got.size(), hipMemcpyDeviceToHost));
-    std::vector<FlatView> v((size_t)W);
-    for(int r = 0; r < W; r++) if(!unpack(got.data() + at[(size_t)r], all[(size_t)r], v[(size_t)r])) return ald_set_err(ALD_ERR_INVALID, "ald_comm_gather_sets: the set of rank " + std::to_string(r) + " arrived damaged");
-    // W-way merge by hash: the ranks' hashes ascend and are disjoint, so the next bucket is the smallest head, taken whole
-    int64_t N = 0, NE = 0, NS = 0; for(auto &x : v) { N += x.n; NE += x.ne; NS += x.ns; }
-    std::vector<int32_t> from((size_t)N); std::vector<int64_t> idx((size_t)N);
-    { std::vector<int64_t> cur((size_t)W, 0);
-      for(int64_t k = 0; k < N; ) {
-          int best = -1;
-          for(int r = 0; r < W; r++) if(cur[(size_t)r] < v[(size_t)r].n && (best < 0 || v[(size_t)r].hash[cur[(size_t)r]] < v[(size_t)best].hash[cur[(size_t)best]])) best = r;
-          const FlatView &x = v[(size_t)best]; int64_t &i = cur[(size_t)best]; const uint64_t h = x.hash[i];
-          while(i < x.n && x.hash[i] == h) { from[(size_t)k] = best; idx[(size_t)k] = i; k++; i++; }
-      } }
-    std::unique_ptr<ald_tset_flat> Fp(new ald_tset_flat()); ald_tset_flat *F = Fp.get();
-    const size_t NT = (size_t)N;
-    F->hash.resize(NT); F->count.resize(NT); F->strand.resize(NT); F->coverage.resize(NT); F->cov2.resize(NT); F->conf.resize(NT); F->abd.resize(NT); F->count1.resize(NT); F->count2.resize(NT); F->tid.resize(NT);
-    F->exon_offset.assign(NT + 1, 0); F->sample_offset.assign(NT + 1, 0);
-    F->exon_lr.resize(2 * (size_t)NE); F->sample_sid.resize((size_t)NS); F->sample_count1.resize((size_t)NS); F->sample_cov2.resize((size_t)NS); F->sample_conf.resize((size_t)NS); F->sample_abd.resize((size_t)NS);
-    for(size_t k = 0; k < NT; k++) {
-        const FlatView &x = v[(size_t)from[k]]; const int64_t i = idx[k];
-        F->hash[k] = x.hash[i]; F->count[k] = x.count[i]; F->strand[k] = x.strand[i]; F->coverage[k] = x.coverage[i]; F->cov2[k] = x.cov2[i]; F->conf[k] = x.conf[i]; F->abd[k] = x.abd[i];
-        F->count1[k] = x.count1[i]; F->count2[k] = x.count2[i]; F->tid[k] = x.tid[i];
-        const int64_t e0 = x.exon_offset[i], e1 = x.exon_offset[i + 1], s0 = x.sample_offset[i], s1 = x.sample_offset[i + 1];
-        const int64_t eo = F->exon_offset[k], so = F->sample_offset[k];
-        if(e0 < 0 || e1 < e0 || e1 > x.ne || s0 < 0 || s1 < s0 || s1 > x.ns || eo + (e1 - e0) > NE || so + (s1 - s0) > NS) return ald_set_err(ALD_ERR_INVALID, "ald_comm_gather_sets: inconsistent offsets in a received set");
-        F->exon_offset[k + 1] = eo + (e1 - e0); F->sample_offset[k + 1] = so + (s1 - s0);
-        if(e1 > e0) memcpy(&F->exon_lr[2 * (size_t)eo], x.exon_lr + 2 * e0, 8 * (size_t)(e1 - e0));
-        for(int64_t s = s0; s < s1; s++) { const size_t d = (size_t)(so + (s - s0)); F->sample_sid[d] = x.sample_sid[s]; F->sample_count1[d] = x.sample_count1[s]; F->sample_cov2[d] = x.sample_cov2[s]; F->sample_conf[d] = x.sample_conf[s]; F->sample_abd[d] = x.sample_abd[s]; }
-        F->n_host_items++;
+    std::vector<FlatView> v((size_t)W); std::vector<HashRun> heads; int64_t N = 0, NE = 0, NS = 0;
+    for(int r = 0; r < W; r++) {
+        FlatView &x = v[(size_t)r];
+        if(!flat_unpack(got.data() + at[(size_t)r], all[(size_t)r], x)) return ald_set_err(ALD_ERR_INVALID, "ald_comm_gather_sets: the set of rank " + std::to_string(r) + " arrived damaged");
+        heads.push_back(HashRun{x.hash, x.n}); N += x.n; NE += x.ne; NS += x.ns;
     }
+    // W-way merge by hash: the ranks' hashes ascend and are disjoint, so the next bucket is the smallest head, taken whole
+    std::unique_ptr<ald_tset_flat> Fp(new ald_tset_flat()); ald_tset_flat *F = Fp.get();
+    flat_resize(*F, N, NE, NS);
+    const FlatMut Fv = flat_mut(*F); int64_t k = 0;
+    for(const auto &src : merge_order(heads)) {
+        const FlatView &x = v[(size_t)src.first]; const int64_t i = src.second;
+        const int64_t e0 = x.exon_offset[i], e1 = x.exon_offset[i + 1], s0 = x.sample_offset[i], s1 = x.sample_offset[i + 1], eo = F->exon_offset[(size_t)k], so = F->sample_offset[(size_t)k];
+        if(e0 < 0 || e1 < e0 || e1 > x.ne || s0 < 0 || s1 < s0 || s1 > x.ns || eo + (e1 - e0) > NE || so + (s1 - s0) > NS) return ald_set_err(ALD_ERR_INVALID, "ald_comm_gather_sets: inconsistent offsets in a received set");
+        flat_copy_row(Fv, k++, x, i);
+    }
+    F->n_host_items = N;
     *out = Fp.release();
     return ALD_OK;
 }

@@ -34,6 +34,8 @@ ALD_HD constexpr int rec_f64_slot(int word) { return (word - ALD_REC_WEIGHT) / 2
 // (tx_build, tx_fold and tx_sfold keep their memcpy into a declared double, with the named words: through rec_f64 the compiler emits
 // different -- shorter -- loads for them, and a change of names is to leave every kernel as it was)
 ALD_HD static inline double rec_f64(const uint32_t *r, int word) { double v; memcpy(&v, r + word, 8); return v; }
+// the id of the transcript a path becomes; label: the graph id that goes into it (the graph's index, or what the caller numbers it)
+ALD_HD static inline int64_t transcript_tid(int64_t tid_base, int64_t label, int64_t path) { return tid_base + ((label << 20) | path); }
 
 // ---- transcript-stream record.  ts_words reads the header only: the caller checks that header and record lie inside its stream
 ALD_HD static inline double ts_f64(const uint32_t *w, int word) { double v; memcpy(&v, w + word, 8); return v; }

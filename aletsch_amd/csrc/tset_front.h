@@ -3,6 +3,7 @@
 // into a set that stays in HBM across calls.  Not installed, not part of the ABI.
 #pragma once
 #include "ald_internal.h"
+#include "tset_flat.h"          // ald_tset_flat, its column view and row operations
 #include <string>
 #include <vector>
 
@@ -140,10 +141,3 @@ struct StreamIndex { const unsigned long long *toff = nullptr; const int32_t *gi
 int tx_stream_index(hipStream_t st, StreamIndexScratch &X, hipEvent_t e0, hipEvent_t e1, const uint32_t *d_words, int64_t n_words, int64_t graph_offset, StreamIndex &I);
 // the path table of a downloaded or finished batch in (graph, path) order on the device (b->d_ordoff), built once per run
 int device_path_table(ald_batch *b);
-
-// the reduced set of one batch, flat, in the reference's iteration order (ascending bucket hash, bucket order inside)
-struct ald_tset_flat {      // (rvec: sized once, every element written by the parallel fill -- no zero pass over ~200 MB first)
-    rvec<uint64_t> hash; rvec<int32_t> count, count1, count2; rvec<char> strand; rvec<double> coverage, cov2, conf, abd; rvec<int64_t> tid; std::vector<int64_t> exon_offset, sample_offset;
-    rvec<int32_t> exon_lr, sample_sid, sample_count1; rvec<double> sample_cov2, sample_conf, sample_abd;
-    double device_ms = 0, host_ms = 0; int64_t n_device_groups = 0, n_host_items = 0;
-};

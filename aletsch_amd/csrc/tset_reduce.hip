@@ -341,7 +341,7 @@ void tx_host_singles(aletsch::transcript_sink &into, const std::vector<int64_t> 
         const uint32_t *r = rec_at(a); const int g = (int)r[ALD_REC_GRAPH];
         const double abd = rec_f64(r, ALD_REC_ABD), conf = rec_f64(r, ALD_REC_CONF);
         x.strand = (char)rec_strand(r); x.coverage = h_cov[(size_t)p]; x.top.cov2 = x.coverage; x.top.conf = conf; x.top.abd = abd; x.top.count1 = (int32_t)r[ALD_REC_COUNT]; x.count2 = 1;
-        x.tid = h_tid ? h_tid[(size_t)p] : tid_base + (((label ? label[g] : (int64_t)g) << 20) | (int64_t)r[ALD_REC_PATH]);
+        x.tid = h_tid ? h_tid[(size_t)p] : transcript_tid(tid_base, label ? label[g] : (int64_t)g, (int64_t)r[ALD_REC_PATH]);
         const int32_t *ex = rec_exons(r); x.xs.assign(ex, ex + r[ALD_REC_NEXW]);
     };
     for(size_t a = 0; a < host_paths.size(); ) {          // one per-graph set per graph that has any (assembler.cc:1105-1133)
@@ -439,28 +439,24 @@ int reduce_core(RedScratch S, const uint32_t *d_pool, const unsigned long long *
         if(j - i > 1) std::stable_sort(order.begin() + (long)i, order.begin() + (long)j, [&](int a, int c) { aletsch::sink_transcript ta, tc; group_tx(a, ta); group_tx(c, tc); return ta.order_against(tc, single_exon_overlap) == +1; });
         i = j;
     }
-    struct HostItem { uint64_t hash; const aletsch::sink_item *z; };
-    std::vector<HostItem> hosts;
-    { std::vector<size_t> keys = single.sorted_keys(); for(size_t key : keys) for(auto &z : single.mt.find(key)->second) hosts.push_back(HostItem{(uint64_t)key, &z}); }
-    const size_t NH = hosts.size(), NT = NG + NH;
-    // final position of every item: device group at sorted rank q goes behind the host items whose hash does not exceed its bucket
+    const SinkRows hosts = sink_rows(&single, 1);
+    const size_t NH = hosts.item.size(), NT = NG + NH;
+    // final position of every item: device group at sorted rank q goes behind the host items whose hash does not exceed its bucket (merge_order's rule, over the group records)
     std::vector<int64_t> pos_dev(NG), pos_host(NH);
-    { size_t h = 0; for(size_t q = 0; q < NG; q++) { const uint64_t bk = groups[(size_t)order[q]].bucket; while(h < NH && hosts[h].hash <= bk) { pos_host[h] = (int64_t)(q + h); h++; } pos_dev[q] = (int64_t)(q + h); } while(h < NH) { pos_host[h] = (int64_t)(NG + h); h++; } }
+    { size_t h = 0; for(size_t q = 0; q < NG; q++) { const uint64_t bk = groups[(size_t)order[q]].bucket; while(h < NH && hosts.hash[h] <= bk) { pos_host[h] = (int64_t)(q + h); h++; } pos_dev[q] = (int64_t)(q + h); } while(h < NH) { pos_host[h] = (int64_t)(NG + h); h++; } }
     F->n_device_groups = (int64_t)NG; F->n_host_items = (int64_t)NH;
-    F->hash.resize(NT); F->count.resize(NT); F->strand.resize(NT); F->coverage.resize(NT); F->cov2.resize(NT); F->conf.resize(NT); F->abd.resize(NT); F->count1.resize(NT); F->count2.resize(NT); F->tid.resize(NT);
-    F->exon_offset.assign(NT + 1, 0); F->sample_offset.assign(NT + 1, 0);
+    flat_resize(*F, (int64_t)NT, 0, 0);
     for(size_t q = 0; q < NG; q++) { const int k = order[q]; F->exon_offset[(size_t)pos_dev[q] + 1] = groups[(size_t)k].nw / 2; F->sample_offset[(size_t)pos_dev[q] + 1] = samp_begin[(size_t)k + 1] - samp_begin[(size_t)k]; }
-    for(size_t h = 0; h < NH; h++) { F->exon_offset[(size_t)pos_host[h] + 1] = (int64_t)hosts[h].z->trst.n_exons(); F->sample_offset[(size_t)pos_host[h] + 1] = (int64_t)hosts[h].z->samples.size(); }
+    for(size_t h = 0; h < NH; h++) { F->exon_offset[(size_t)pos_host[h] + 1] = (int64_t)hosts.item[h]->trst.n_exons(); F->sample_offset[(size_t)pos_host[h] + 1] = (int64_t)hosts.item[h]->samples.size(); }
     for(size_t i = 0; i < NT; i++) { F->exon_offset[i + 1] += F->exon_offset[i]; F->sample_offset[i + 1] += F->sample_offset[i]; }
-    F->exon_lr.resize(2 * (size_t)F->exon_offset[NT]); const size_t NS = (size_t)F->sample_offset[NT];
-    F->sample_sid.resize(NS); F->sample_count1.resize(NS); F->sample_cov2.resize(NS); F->sample_conf.resize(NS); F->sample_abd.resize(NS);
+    flat_resize(*F, (int64_t)NT, F->exon_offset[NT], F->sample_offset[NT]);
     const auto T4 = std::chrono::steady_clock::now();
     unsigned fthr = std::thread::hardware_concurrency(); if(fthr == 0) fthr = 1; if(fthr > 16) fthr = 16; if(NG < 50000) fthr = 1;
     HostBatch::run_threads(fthr, [&](unsigned t) {
         for(size_t q = NG * t / fthr; q < NG * (t + 1) / fthr; q++) {
             const int k = order[q]; const TxGroup &G = groups[(size_t)k]; const size_t i = (size_t)pos_dev[q];
             F->hash[i] = G.bucket; F->count[i] = G.count; F->strand[i] = (char)G.strand; F->coverage[i] = G.coverage; F->cov2[i] = G.cov2; F->conf[i] = G.conf; F->abd[i] = G.abd; F->count1[i] = G.count1;
-            F->tid[i] = h_tid ? h_tid[(size_t)G.first] : tid_base + ((graph_label(G.graph) << 20) | (int64_t)G.path);
+            F->tid[i] = h_tid ? h_tid[(size_t)G.first] : transcript_tid(tid_base, graph_label(G.graph), (int64_t)G.path);
             int32_t *e = &F->exon_lr[2 * (size_t)F->exon_offset[i]];
             memcpy(e, group_exons(G), 4 * (size_t)G.nw); e[0] = G.lo; e[G.nw - 1] = G.hi;
             size_t so = (size_t)F->sample_offset[i]; int c2 = 0;
@@ -471,14 +467,7 @@ int reduce_core(RedScratch S, const uint32_t *d_pool, const unsigned long long *
             F->count2[i] = c2;
         }
     });
-    for(size_t h = 0; h < NH; h++) {
-        const aletsch::sink_item &z = *hosts[h].z; const aletsch::sink_transcript &r = z.trst; const size_t i = (size_t)pos_host[h];
-        F->hash[i] = hosts[h].hash; F->count[i] = z.count; F->strand[i] = r.strand; F->coverage[i] = r.coverage; F->cov2[i] = r.top.cov2; F->conf[i] = r.top.conf; F->abd[i] = r.top.abd;
-        F->count1[i] = r.top.count1; F->count2[i] = r.count2; F->tid[i] = r.tid;
-        if(!r.xs.empty()) memcpy(&F->exon_lr[2 * (size_t)F->exon_offset[i]], r.xs.data(), 4 * r.xs.size());
-        size_t so = (size_t)F->sample_offset[i];
-        for(auto &q : z.samples) { F->sample_sid[so] = q.first; F->sample_cov2[so] = q.second.top.cov2; F->sample_conf[so] = q.second.top.conf; F->sample_abd[so] = q.second.top.abd; F->sample_count1[so] = q.second.top.count1; so++; }
-    }
+    { const FlatMut V = flat_mut(*F); for(size_t h = 0; h < NH; h++) flat_put_item(V, pos_host[h], hosts.hash[h], *hosts.item[h]); }
     F->host_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - T0).count();
     if(getenv("ALD_SINK_PROF")) { auto ms = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point c) { return std::chrono::duration<double, std::milli>(c - a).count(); };
         fprintf(stderr, "[reduce] setup %.1f ms, device section %.1f ms (events %.1f), single-exon host %.1f ms, order + offsets %.1f ms, fill %.1f ms\n", ms(T0, T1), ms(T1, T2), F->device_ms, ms(T2, T3), ms(T3, T4), ms(T4, std::chrono::steady_clock::now())); }
@@ -581,14 +570,11 @@ int ald_tset_flat_export(const ald_tset_flat *f, uint64_t *hash, int32_t *count,
                          int32_t *count1, int32_t *count2, int64_t *tid, int64_t *exon_offset, int32_t *exon_lr,
                          int64_t *sample_offset, int32_t *sample_sid, double *sample_cov2, double *sample_conf, double *sample_abd, int32_t *sample_count1)
 {
-    if(!f || !hash || !count || !strand || !coverage || !cov2 || !conf || !abd || !count1 || !count2 || !tid || !exon_offset || !exon_lr || !sample_offset || !sample_sid || !sample_cov2 || !sample_conf || !sample_abd || !sample_count1) return ALD_ERR_INVALID;
-    const size_t n = f->hash.size();
-#define ALD_CP(dst, src) if(!(src).empty()) memcpy(dst, (src).data(), sizeof((src)[0]) * (src).size())
-    ALD_CP(hash, f->hash); ALD_CP(count, f->count); ALD_CP(strand, f->strand); ALD_CP(coverage, f->coverage); ALD_CP(cov2, f->cov2); ALD_CP(conf, f->conf); ALD_CP(abd, f->abd);
-    ALD_CP(count1, f->count1); ALD_CP(count2, f->count2); ALD_CP(tid, f->tid); ALD_CP(exon_offset, f->exon_offset); ALD_CP(exon_lr, f->exon_lr); ALD_CP(sample_offset, f->sample_offset);
-    ALD_CP(sample_sid, f->sample_sid); ALD_CP(sample_cov2, f->sample_cov2); ALD_CP(sample_conf, f->sample_conf); ALD_CP(sample_abd, f->sample_abd); ALD_CP(sample_count1, f->sample_count1);
-#undef ALD_CP
-    (void)n;
+    if(!f) return ALD_ERR_INVALID;
+    const FlatView src = flat_view(*f);
+    const FlatMut dst{hash, count, strand, coverage, cov2, conf, abd, count1, count2, tid, exon_offset, exon_lr, sample_offset, sample_sid, sample_cov2, sample_conf, sample_abd, sample_count1, src.n, src.ne, src.ns};
+    if(flat_has_null(dst)) return ALD_ERR_INVALID;
+    flat_copy(dst, src);
     return ALD_OK;
 }
 int ald_tset_flat_free(ald_tset_flat *f) { delete f; return ALD_OK; }
@@ -597,7 +583,7 @@ int ald_tset_flat_free(ald_tset_flat *f) { delete f; return ALD_OK; }
 int ald_tset_add_flat(ald_tset *t, const ald_tset_flat *f)
 {
     if(!t || !f) return ALD_ERR_INVALID;
-    const size_t n = f->hash.size();
+    const FlatView v = flat_view(*f); const size_t n = (size_t)v.n;
     // buckets never interact and bucket h lives in table h % ALD_TSET_SHARDS: thread th zips the buckets of ITS tables (every thread
     // scans the hashes, which are ascending; building the items is the work)
     const unsigned nthr = ald_sink_threads((int64_t)n);
@@ -606,17 +592,7 @@ int ald_tset_add_flat(ald_tset *t, const ald_tset_flat *f)
             size_t j = i + 1; while(j < n && f->hash[j] == f->hash[i]) j++;
             if((f->hash[i] % ALD_TSET_SHARDS) % nthr != th) { i = j; continue; }
             aletsch::transcript_sink::bucket vec;
-            for(size_t k = i; k < j; k++) {
-                aletsch::sink_item z; aletsch::sink_transcript &r = z.trst;
-                r.strand = f->strand[k]; r.coverage = f->coverage[k]; r.top.cov2 = f->cov2[k]; r.top.conf = f->conf[k]; r.top.abd = f->abd[k]; r.top.count1 = f->count1[k]; r.count2 = f->count2[k]; r.tid = f->tid[k];
-                r.xs.assign(f->exon_lr.begin() + 2 * f->exon_offset[k], f->exon_lr.begin() + 2 * f->exon_offset[k + 1]);
-                z.count = f->count[k];
-                for(int64_t s = f->sample_offset[k]; s < f->sample_offset[k + 1]; s++) {
-                    aletsch::sink_sample x; x.coverage = r.coverage; x.top.cov2 = f->sample_cov2[(size_t)s]; x.top.conf = f->sample_conf[(size_t)s]; x.top.abd = f->sample_abd[(size_t)s]; x.top.count1 = f->sample_count1[(size_t)s]; x.count2 = r.count2;
-                    bool fresh; z.samples.slot(f->sample_sid[(size_t)s], x, fresh);
-                }
-                vec.push_back(std::move(z));
-            }
+            for(size_t k = i; k < j; k++) vec.push_back(flat_get_item(v, (int64_t)k));
             t->shard[f->hash[i] % ALD_TSET_SHARDS].add_bucket((size_t)f->hash[i], vec);
             i = j;
         }

@@ -52,6 +52,9 @@ struct SetBufs {
         v.abd = (double*)abd.p; v.count1 = (int32_t*)count1.p; v.tid = (int64_t*)tid.p; v.eoff = (int64_t*)eoff.p; v.lr = (int32_t*)lr.p; v.soff = (int64_t*)soff.p;
         v.ssid = (int32_t*)ssid.p; v.sc1 = (int32_t*)sc1.p; v.scov2 = (double*)scov2.p; v.sconf = (double*)sconf.p; v.sabd = (double*)sabd.p; v.n = n; return v;
     }
+    // the same buffers under the names of the flat set's columns (tset_flat.h; DEVICE pointers).  count2 is not stored: #samples
+    FlatView flat() const { return FlatView{(const uint64_t*)hash.p, (const int32_t*)count.p, (const char*)strand.p, (const double*)cov.p, (const double*)cov2.p, (const double*)conf.p, (const double*)abd.p, (const int32_t*)count1.p, nullptr,
+                        (const int64_t*)tid.p, (const int64_t*)eoff.p, (const int32_t*)lr.p, (const int64_t*)soff.p, (const int32_t*)ssid.p, (const double*)scov2.p, (const double*)sconf.p, (const double*)sabd.p, (const int32_t*)sc1.p, n, ne, ns}; }
     int ensure_items(int64_t k) {    // k items (+1 offset entry)
         const size_t m = (size_t)k + 1;
         return hash.ensure(8 * m) || count.ensure(4 * m) || strand.ensure(m) || cov.ensure(8 * m) || cov2.ensure(8 * m) || conf.ensure(8 * m) || abd.ensure(8 * m)
@@ -96,7 +99,7 @@ struct InBatch {                     // a batch's groups: before the fold only h
     __device__ double conf(int64_t j) const { return grp[perm[j]].conf; }
     __device__ double abd(int64_t j) const { return grp[perm[j]].abd; }
     __device__ int32_t count1(int64_t j) const { return grp[perm[j]].count1; }
-    __device__ int64_t tid(int64_t j) const { const TxGroup &G = grp[perm[j]]; return ptid ? ptid[G.first] : tid_base + (((label ? label[G.graph] : (int64_t)G.graph) << 20) | (int64_t)G.path); }
+    __device__ int64_t tid(int64_t j) const { const TxGroup &G = grp[perm[j]]; return ptid ? ptid[G.first] : transcript_tid(tid_base, label ? label[G.graph] : (int64_t)G.graph, (int64_t)G.path); }
     __device__ int64_t sb(int64_t j) const { return sbeg[perm[j]]; }
     __device__ int64_t se(int64_t j) const { return sbeg[perm[j] + 1]; }
     __device__ void sample(int64_t s, int32_t &sid, double &c2, double &cf, double &ab, int32_t &c1) const { const TxSample &S = smp[s]; sid = S.sid; c2 = S.cov2; cf = S.conf; ab = S.abd; c1 = S.count1; }
@@ -463,66 +466,35 @@ int add_device_stream(ald_tset_dev *s, const uint32_t *d_words, int64_t n_words,
 }
 
 // The device part, copied back: flat arrays in the set's order (exon / sample offsets included), count2 = #samples
-int fetch_device_part(const ald_tset_dev *cs, ald_tset_flat &D)
+int fetch_device_part(const ald_tset_dev *s, ald_tset_flat &D)
 {
-    ald_tset_dev *s = const_cast<ald_tset_dev*>(cs);
-    const SetBufs &R = s->res(); const int64_t n = R.n, ne = R.ne, ns = R.ns;
-    hipStream_t st = s->st;
-    D.hash.resize((size_t)n); D.count.resize((size_t)n); D.strand.resize((size_t)n); D.coverage.resize((size_t)n); D.cov2.resize((size_t)n); D.conf.resize((size_t)n); D.abd.resize((size_t)n);
-    D.count1.resize((size_t)n); D.count2.resize((size_t)n); D.tid.resize((size_t)n); D.exon_offset.assign((size_t)n + 1, 0); D.sample_offset.assign((size_t)n + 1, 0);
-    D.exon_lr.resize(2 * (size_t)ne); D.sample_sid.resize((size_t)ns); D.sample_count1.resize((size_t)ns); D.sample_cov2.resize((size_t)ns); D.sample_conf.resize((size_t)ns); D.sample_abd.resize((size_t)ns);
-    if(n == 0) return ALD_OK;
-    auto get = [&](void *dst, const DevBuf &src, size_t bytes) { return bytes ? hipMemcpyAsync(dst, src.p, bytes, hipMemcpyDeviceToHost, st) : hipSuccess; };
-    HCHK(get(D.hash.data(), R.hash, 8 * (size_t)n)); HCHK(get(D.count.data(), R.count, 4 * (size_t)n)); HCHK(get(D.strand.data(), R.strand, (size_t)n));
-    HCHK(get(D.coverage.data(), R.cov, 8 * (size_t)n)); HCHK(get(D.cov2.data(), R.cov2, 8 * (size_t)n)); HCHK(get(D.conf.data(), R.conf, 8 * (size_t)n)); HCHK(get(D.abd.data(), R.abd, 8 * (size_t)n));
-    HCHK(get(D.count1.data(), R.count1, 4 * (size_t)n)); HCHK(get(D.tid.data(), R.tid, 8 * (size_t)n));
-    HCHK(get(D.exon_offset.data(), R.eoff, 8 * ((size_t)n + 1))); HCHK(get(D.sample_offset.data(), R.soff, 8 * ((size_t)n + 1)));
-    HCHK(get(D.exon_lr.data(), R.lr, 8 * (size_t)ne)); HCHK(get(D.sample_sid.data(), R.ssid, 4 * (size_t)ns)); HCHK(get(D.sample_count1.data(), R.sc1, 4 * (size_t)ns));
-    HCHK(get(D.sample_cov2.data(), R.scov2, 8 * (size_t)ns)); HCHK(get(D.sample_conf.data(), R.sconf, 8 * (size_t)ns)); HCHK(get(D.sample_abd.data(), R.sabd, 8 * (size_t)ns));
-    HCHK(hipStreamSynchronize(st));
-    for(int64_t i = 0; i < n; i++) D.count2[(size_t)i] = (int32_t)(D.sample_offset[(size_t)i + 1] - D.sample_offset[(size_t)i]);
+    const FlatView R = s->res().flat();
+    flat_resize(D, R.n, R.ne, R.ns);
+    if(R.n == 0) return ALD_OK;
+    hipError_t e = hipSuccess;
+    for_each_column([&](FlatKind k, auto *dst, auto *src) { if(src && R.len(k) && e == hipSuccess) e = hipMemcpyAsync(dst, src, sizeof(*src) * R.len(k), hipMemcpyDeviceToHost, s->st); }, flat_mut(D), R);
+    if(e != hipSuccess) return ald_set_err(ALD_ERR_HIP, std::string("resident set, device to host: ") + hipGetErrorString(e));
+    HCHK(hipStreamSynchronize(s->st));
+    for(int64_t i = 0; i < R.n; i++) D.count2[(size_t)i] = (int32_t)(D.sample_offset[(size_t)i + 1] - D.sample_offset[(size_t)i]);
     return ALD_OK;
-}
-
-// item i of flat set `S` appended to F (offsets of F kept as running totals in F.exon_offset / F.sample_offset's last entry)
-void append_item(ald_tset_flat &F, const ald_tset_flat &S, size_t i)
-{
-    F.hash.push_back(S.hash[i]); F.count.push_back(S.count[i]); F.strand.push_back(S.strand[i]); F.coverage.push_back(S.coverage[i]); F.cov2.push_back(S.cov2[i]);
-    F.conf.push_back(S.conf[i]); F.abd.push_back(S.abd[i]); F.count1.push_back(S.count1[i]); F.count2.push_back(S.count2[i]); F.tid.push_back(S.tid[i]);
-    F.exon_lr.insert(F.exon_lr.end(), S.exon_lr.begin() + 2 * S.exon_offset[i], S.exon_lr.begin() + 2 * S.exon_offset[i + 1]);
-    F.exon_offset.push_back(F.exon_offset.back() + S.exon_offset[i + 1] - S.exon_offset[i]);
-    for(int64_t q = S.sample_offset[i]; q < S.sample_offset[i + 1]; q++) {
-        F.sample_sid.push_back(S.sample_sid[(size_t)q]); F.sample_cov2.push_back(S.sample_cov2[(size_t)q]); F.sample_conf.push_back(S.sample_conf[(size_t)q]);
-        F.sample_abd.push_back(S.sample_abd[(size_t)q]); F.sample_count1.push_back(S.sample_count1[(size_t)q]);
-    }
-    F.sample_offset.push_back(F.sample_offset.back() + S.sample_offset[i + 1] - S.sample_offset[i]);
 }
 
 // the whole set, flat, in the reference's iteration order: the host items (fewer than two exons) spliced in by hash, ahead of the device
 // items of the same hash (compare1 puts fewer exons first, transcript.cc:271)
 int snapshot(const ald_tset_dev *s, ald_tset_flat &F)
 {
-    ald_tset_flat D, H;
+    ald_tset_flat D;
     { int rc = fetch_device_part(s, D); if(rc != ALD_OK) return rc; }
-    H.exon_offset.push_back(0); H.sample_offset.push_back(0);
-    for(size_t key : s->single.sorted_keys()) for(auto &z : s->single.mt.find(key)->second) {
-        const aletsch::sink_transcript &r = z.trst;
-        H.hash.push_back(key); H.count.push_back(z.count); H.strand.push_back(r.strand); H.coverage.push_back(r.coverage); H.cov2.push_back(r.top.cov2); H.conf.push_back(r.top.conf);
-        H.abd.push_back(r.top.abd); H.count1.push_back(r.top.count1); H.count2.push_back(r.count2); H.tid.push_back(r.tid);
-        H.exon_lr.insert(H.exon_lr.end(), r.xs.begin(), r.xs.end()); H.exon_offset.push_back(H.exon_offset.back() + (int64_t)r.n_exons());
-        for(auto &q : z.samples) { H.sample_sid.push_back(q.first); H.sample_cov2.push_back(q.second.top.cov2); H.sample_conf.push_back(q.second.top.conf); H.sample_abd.push_back(q.second.top.abd); H.sample_count1.push_back(q.second.top.count1); }
-        H.sample_offset.push_back(H.sample_offset.back() + (int64_t)z.samples.size());
-    }
-    const size_t NG = D.hash.size(), NH = H.hash.size();
+    const SinkRows H = sink_rows(&s->single, 1);
+    const FlatView Dv = flat_view(D); const int64_t NG = Dv.n, NH = (int64_t)H.item.size();
     if(NH == 0) F = std::move(D);
     else {
-        F.exon_offset.push_back(0); F.sample_offset.push_back(0);
-        for(size_t h = 0, i = 0; h < NH || i < NG; ) {
-            if(h < NH && (i >= NG || H.hash[h] <= D.hash[i])) append_item(F, H, h++);
-            else append_item(F, D, i++);
-        }
+        flat_resize(F, NG + NH, Dv.ne + H.ne, Dv.ns + H.ns);
+        const FlatMut Fv = flat_mut(F); int64_t k = 0;
+        for(const auto &at : merge_order({HashRun{H.hash.data(), NH}, HashRun{Dv.hash, NG}}))
+            if(at.first == 0) flat_put_item(Fv, k++, H.hash[(size_t)at.second], *H.item[(size_t)at.second]); else flat_copy_row(Fv, k++, Dv, at.second);
     }
-    F.n_device_groups = (int64_t)NG; F.n_host_items = (int64_t)NH;
+    F.n_device_groups = NG; F.n_host_items = NH;
     return ALD_OK;
 }
 

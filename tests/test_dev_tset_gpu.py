@@ -110,6 +110,34 @@ def test_merge_and_snapshot():
         assert _gtf(got) == _gtf(want)
 
 
+@pytest.mark.parametrize("shape", ("device part only", "both parts", "host part only", "empty"))
+def test_the_four_shapes_of_a_snapshot(shape):
+    """snapshot() has a device part, a host part (fewer than two exons), both or neither.  Collide case 0 -- single-exon items and chains
+    share buckets there -- with and without the single-exon filter, its single-exon transcripts alone, and an empty stream: the export of
+    the resident set, its snapshot zipped into an empty host sink and the reduction into an empty set give the same items, which are the
+    reference's stored ones (for the host part alone: a host sink's, which the CPU tier pins to the reference)"""
+    from test_tset_collide_cpu import golden
+    groups, want = golden()[0]
+    singles = [g for g in ((sid, [t for t in ts if len(t[6]) == 1]) for sid, ts in groups) if g[1]]
+    gs, skip = {"device part only": (groups, True), "both parts": (groups, False), "host part only": (singles, False), "empty": ([], False)}[shape]
+    w, c, t = stream_of(gs, 0)
+    with A.DeviceTranscriptSet(0, 0.8) as ds:
+        ds.add_stream(w, coverage=c, tid=t, skip_single_exon=skip)
+        exported = ds.items(); st = ds.stats(); size = ds.size()
+        flat = A.TranscriptSink(0.8); ds.snapshot_into(flat)
+    reduced, _ = A.reduce_stream(w, coverage=c, tid=t, skip_single_exon=skip)
+    assert exported == flat.items() and exported == reduced
+    assert (st["device_items"] > 0) == (shape in ("device part only", "both parts")) and (st["host_items"] > 0) == (shape in ("both parts", "host part only"))
+    assert size[0] == len(exported) and size[1] == sum(len(x["exons"]) for x in exported) and size[2] == sum(len(x["samples"]) for x in exported)
+    if shape == "empty":
+        assert exported == [] and size == (0, 0, 0)
+    elif shape == "host part only":
+        host = A.TranscriptSink(0.8); host.add_groups(singles)
+        assert exported == host.items() and len(exported) > 0
+    else:
+        check(exported, want["seq_multi" if skip else "seq"])
+
+
 def test_edge_cases():
     import ctypes
     base = _base()
