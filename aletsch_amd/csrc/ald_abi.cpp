@@ -436,10 +436,11 @@ int ald_batch_upload(ald_batch *b)
     {
         b->cls0.assign(n, -1);
         std::vector<int32_t> work[ALD_NUM_CLASSES];
+        const int first = debug_first_class();       // ALD_DEBUG_FIRST_CLASS (tests): 0 when unset
         for(int g = 0; g < n; g++) {
             int64_t ns = b->hb.off_s[g + 1] - b->hb.off_s[g], npv = b->hb.off_pv[g + 1] - b->hb.off_pv[g];
             if(b->hb.g_rawdist[g] >= 0) npv += 2 * (b->hb.off_rc[g + 1] - b->hb.off_rc[g]);      // a raw graph's lists do not exist yet: an estimate (too small a class is retried one up)
-            int c = debug_underclass(pick_class(b->hb.g_nv[g], b->hb.g_ne[g], ns, npv));
+            int c = debug_underclass(pick_class(b->hb.g_nv[g], b->hb.g_ne[g], ns, npv, first));
             b->cls0[g] = c;
             if(c >= 0) work[c].push_back(g);
         }

@@ -323,6 +323,15 @@ static inline int debug_underclass(int c)
     if(c < 0 || k <= 0) return c;
     return c - k < 0 ? 0 : c - k;
 }
+// test knob: ALD_DEBUG_FIRST_CLASS=c is the `first` of pick_class for every graph of the batch, so that small graphs run in the kernel of
+// class c (a graph that does not fit c goes further up as usual; 13 is the class beyond the catch-all; the twins 11 / 12 are reached as
+// 7 / 8 with ALD_DEBUG_TWIN=1).  Unset: 0, the smallest class that holds the graph.
+static inline int debug_first_class()
+{
+    const char *e = getenv("ALD_DEBUG_FIRST_CLASS");
+    const int c = e ? atoi(e) : 0;
+    return c > 0 ? c : 0;
+}
 #endif
 
 } // namespace ald

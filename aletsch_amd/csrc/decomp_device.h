@@ -147,6 +147,13 @@ struct HotCtx {
 #endif
 };
 
+// Two things follow from "the hot state of this class lives in the wave's slab", and they are named apart: WHERE Hot is (ALD_HOT_IN_SLAB, below:
+// device builds only -- the single-lane emulation keeps it in a plain static whatever the class) and WHICH FORM the list walks of
+// eval_smallest / compute_balance_ratio take (ALD_MERGED_WALKS: the in- and the out-list advance together), which the emulation of these
+// classes compiles as well, so that the CPU tier runs the walks the device runs.
+#if ALD_CLASS_ID >= ALD_FIRST_GLOBAL_CLASS
+#define ALD_MERGED_WALKS 1
+#endif
 #if defined(ALD_EMU)
 static thread_local Hot g_H;
 static thread_local HotCtx g_HC;
@@ -2017,7 +2024,7 @@ ALD_FN int classify_trivial_vertex(int x, bool fast)     // scalar version with 
 }
 ALD_INL double compute_balance_ratio(int v, bool &ok)    // scallop.cc:2578-2602
 {
-#ifndef ALD_HOT_IN_SLAB
+#ifndef ALD_MERGED_WALKS
     double w1 = in_weights(v), w2 = out_weights(v);
 #else
     double w1 = 0, w2 = 0;
@@ -2060,7 +2067,7 @@ ALD_INL int eval_smallest(int i, double &r)
         hin = slot_or_neg(vr.in_head); hout = slot_or_neg(vr.out_head);
     }
     int e1 = -1, e2 = -1; double sum1 = 0, sum2 = 0, min1 = DBL_MAX, min2 = DBL_MAX;
-#ifndef ALD_HOT_IN_SLAB
+#ifndef ALD_MERGED_WALKS
     for(int e = hin; e >= 0; e = next_in(e)) { double w = H.ed[e].w; sum1 += w; if(w > min1) continue; min1 = w; e1 = e; }
     for(int e = hout; e >= 0; e = next_out(e)) { double w = H.ed[e].w; sum2 += w; if(w > min2) continue; min2 = w; e2 = e; }
 #else

@@ -126,10 +126,11 @@ def emu_run(pg: PackedGraphs, trace_cap: int = 0, force_class: int = 0, params=N
     return r, it, cl
 
 
-def emu_run_raw(items, params=None):
+def emu_run_raw(items, params=None, force_class: int = 0, trace_cap: int = 0, full: bool = False):
     """items: [(single-graph PackedGraphs, phases, max_group_boundary_distance), ...] as assembler::assemble(gx, px, sid) receives them;
     staged raw (HostBatch::add_graph_raw) and run through the single-lane emulation of the engine, whose load phase does the pre-steps
-    -> (DecompResult, iterations[n])"""
+    -> (DecompResult, iterations[n]); force_class: the first class pick_class may choose (the class of a small graph); full
+    -> (DecompResult, iterations[n], class[n], op traces or None when trace_cap == 0)"""
     from aletsch_amd.native import GraphView, PhaseView
     E = emu_lib()
     E.emu_batch_new.restype = C.c_void_p
@@ -142,15 +143,37 @@ def emu_run_raw(items, params=None):
             rc = E.emu_batch_add_raw(B, C.byref(gv), C.byref(pv), C.c_int32(dist))
             assert rc == 0, rc
         h = C.c_void_p()
-        rc = E.emu_batch_run(B, C.byref(params) if params is not None else None, C.c_int32(0), C.c_int32(0), C.byref(h))
+        rc = E.emu_batch_run(B, C.byref(params) if params is not None else None, C.c_int32(trace_cap), C.c_int32(force_class), C.byref(h))
         assert rc == 0, rc
         r = export_via(E.emu_result_export, h, len(items))
         it = np.zeros(len(items), np.int32); cl = np.zeros(len(items), np.int32)
         E.emu_result_iters(h, it.ctypes.data_as(C.POINTER(C.c_int32)), cl.ctypes.data_as(C.POINTER(C.c_int32)))
+        traces = [emu_trace_of(E, h, g, trace_cap) for g in range(len(items))] if trace_cap > 0 else None
         E.emu_result_free(h)
     finally:
         E.emu_batch_free(B)
-    return r, it
+    return (r, it, cl, traces) if full else (r, it)
+
+
+def emu_traces(pg: PackedGraphs, cap: int = 1 << 13, force_class: int = 0, params=None, keep: bool = False):
+    """the emulation's op trace of every graph of pg (rule id, vertex or edge id, second id, ratio of every firing, in order)"""
+    E = emu_keep_lib() if keep else emu_lib()
+    h = C.c_void_p()
+    rc = E.emu_run_packed(*pg.c_args(), C.byref(params) if params is not None else None, C.c_int32(cap), C.c_int32(force_class), C.byref(h))
+    assert rc == 0, rc
+    out = [emu_trace_of(E, h, g, cap) for g in range(pg.n)]
+    E.emu_result_free(h)
+    return out
+
+
+def emu_trace_of(E, h, g: int, cap: int):
+    """the op trace of graph g of an emulation result handle: [(code, a, b, value), ...]"""
+    n = C.c_int32()
+    codes = np.zeros(3 * cap, np.int32); vals = np.zeros(cap)
+    E.emu_result_trace(h, C.c_int32(g), C.byref(n), codes.ctypes.data_as(C.POINTER(C.c_int32)), vals.ctypes.data_as(C.POINTER(C.c_double)), C.c_int32(cap))
+    assert n.value <= cap, (g, n.value)
+    k = n.value
+    return [(int(codes[3 * i]), int(codes[3 * i + 1]), int(codes[3 * i + 2]), float(vals[i])) for i in range(k)]
 
 
 def emu_transcripts(pg: PackedGraphs):

@@ -343,9 +343,11 @@ def fan_bucket(fan: int, K: dict) -> str:
 
 
 def class_group(cls: int, nv: int, K: dict) -> str:
-    """0-1 | 2-9 | twins: the groups ALD_STARFIX_MAX distinguishes (a graph of a class that has a twin counts as twin-sized: the twin tests
-    run it on both)"""
+    """0-1 | 2-9 | twins | 10,13: the groups ALD_STARFIX_MAX distinguishes (a graph of a class that has a twin counts as twin-sized: the twin
+    tests run it on both).  The catch-all class and the class beyond it are a group of their own: they share ALD_STARFIX_MAX with classes
+    0 / 1 and nothing else (hot state in the slab, kept sweep records, the merged list walks)."""
     if cls in K["TWINS"] or cls in K["TWINS"].values(): return "twins"
+    if cls >= 10: return "10,13"
     return "0-1" if cls <= 1 else "2-9"
 
 
@@ -403,11 +405,22 @@ class Census:
                 out["fan %s %s" % (fb, d)] = self.fans.get((fb, d), 0)
         for fb in ("2", "3", "4", "5-8"):
             for d in ("in", "out"):
-                for grp in ("0-1", "2-9", "twins"):
+                for grp in ("0-1", "2-9", "twins", "10,13"):
                     out["fan %s %s class %s" % (fb, d, grp)] = self.fans_by_group.get((fb, d, grp), 0)
         for b in self.router_names():
             out["router " + b] = self.routers.get(b, 0)
         return out
+
+    def required_of_group(self, grp: str):
+        """the lines of required() that belong to one class group"""
+        return {k: v for k, v in self.required().items() if k.endswith(" class " + grp)}
+
+    def add_group(self, other: "Census", grp: str):
+        """the fans of ONE class group of another census, nothing else of it (tests/class_cases.py fills the group of classes 10 / 13 with
+        small hubs that are run in those classes; the other lines stay what the hub batch alone gives)"""
+        for k, v in other.fans_by_group.items():
+            if k[2] == grp: self.fans_by_group[k] = self.fans_by_group.get(k, 0) + v
+        return self
 
     def add(self, other: "Census"):
         for mine, theirs in ((self.fans, other.fans), (self.fans_by_group, other.fans_by_group), (self.routers, other.routers)):

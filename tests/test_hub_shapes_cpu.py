@@ -78,12 +78,14 @@ def hub_census():
     _, _, zper = _oracle(zpg)
     zc = shapes.Census(zper, np.zeros(zpg.n, np.int32), zpg.g_nv, K)
     cen.routers["routes, count 0"] = zc.routers.get("routes, count 0", 0)              # (that bucket is filled by the batch whose graphs may end on an assert)
+    import class_cases                                                                 # the group of classes 10 / 13: the small hubs of the class mix, which
+    cen.add_group(class_cases.forced_hub_census(K), "10,13")                           # tests/test_class_matrix_*.py run in those classes (pick_class's first class)
     return cen
 
 
 def test_every_census_bucket_is_filled():
     """Every fan-size bucket in both directions, fans of 2..8 in every class group ALD_STARFIX_MAX distinguishes (graphs of class 0 / 1, of
-    classes 2..9, of twin size), and every router bucket: at least MIN_EVENTS events each, counted by the oracle over the hub batch."""
+    classes 2..9, of twin size, and -- from the class mix -- of classes 10 / 13), and every router bucket: at least MIN_EVENTS events each, counted by the oracle over the hub batch."""
     cen = hub_census()
     print("\ncensus of the hub batch (events per bucket):\n" + cen.table())
     short = {k: v for k, v in cen.required().items() if v < MIN_EVENTS}
