@@ -11,10 +11,10 @@ from .native import (DecompBatch, DecompError, default_params, load_library, lib
                      subsetsum_batch, decompose, SynthSpec, AldParams, TranscriptSink, records_add_graph_offset,
                      TrstFeatures, GraphExtras, BatchExtras, FEATURE_FIELDS, FEATURE_DTYPE, format_transcript, format_features, transcript_id,
                      GraphView, PhaseView, pre_assemble, reduce_stream, DeviceTranscriptSet,
-                     transcript_bucket, split_stream, split_stream_into, index_stream_into)
+                     transcript_bucket, split_stream, split_stream_into, index_stream_into, PARAM_COMPACT_INPUT)
 
 __all__ = ["PackedGraphs", "DecompResult", "DecompBatch", "DecompError", "default_params", "load_library",
            "library_path", "synth", "subsetsum_batch", "decompose", "SynthSpec", "AldParams", "TranscriptSink", "records_add_graph_offset",
            "TrstFeatures", "GraphExtras", "BatchExtras", "FEATURE_FIELDS", "FEATURE_DTYPE", "format_transcript", "format_features", "transcript_id",
            "GraphView", "PhaseView", "pre_assemble", "reduce_stream", "DeviceTranscriptSet",
-           "transcript_bucket", "split_stream", "split_stream_into", "index_stream_into"]
+           "transcript_bucket", "split_stream", "split_stream_into", "index_stream_into", "PARAM_COMPACT_INPUT"]

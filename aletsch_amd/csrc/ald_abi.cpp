@@ -293,6 +293,9 @@ int ald_batch_create(const ald_params *p, int device, ald_batch **out)
     g_live_batches.fetch_add(1);
     b->device = device; b->n_cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
     params_from_abi(p, b->prm);
+    // compact input: bit 0 of ald_params.reserved; ALD_COMPACT_INPUT=1 / 0 forces it on / off for every batch of the process
+    b->hb.compact = p && (p->reserved & ALD_PARAM_COMPACT_INPUT);
+    if(const char *ev = getenv("ALD_COMPACT_INPUT")) { if(ev[0] == '1') b->hb.compact = true; else if(ev[0] == '0') b->hb.compact = false; }
     bool ok = hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking) == hipSuccess && hipEventCreate(&b->ev0) == hipSuccess && hipEventCreate(&b->ev1) == hipSuccess;
     if(const char *ev = getenv("ALD_SIDE_STREAMS")) { const int k = atoi(ev); if(k >= 1 && k <= ALD_SIDE_STREAMS_MAX) b->n_cstream = k; }      // tuning knob
     for(int q = 0; q < b->n_cstream && ok; q++) ok = hipStreamCreateWithFlags(&b->cstream[q], hipStreamNonBlocking) == hipSuccess;
@@ -315,7 +318,7 @@ int ald_batch_destroy(ald_batch *b)
     hipSetDevice(b->device);
     if(b->stream) hipStreamSynchronize(b->stream);
     b->pin_in.release(); b->pin_out.release(); b->pin_small.release(); b->pin_index.release(); delete b->pass0; b->pass0 = nullptr;
-    DevBuf *bufs[] = {&b->d_in, &b->d_status, &b->d_npaths, &b->d_niters, &b->d_pool, &b->d_poolused, &b->d_index, &b->d_gfirst, &b->d_pbegin, &b->d_ordoff, &b->d_trace_n, &b->d_trace_codes, &b->d_trace_vals, &b->d_work, &b->d_counter, &b->d_args};
+    DevBuf *bufs[] = {&b->d_in, &b->d_gsid, &b->d_status, &b->d_npaths, &b->d_niters, &b->d_pool, &b->d_poolused, &b->d_index, &b->d_gfirst, &b->d_pbegin, &b->d_ordoff, &b->d_trace_n, &b->d_trace_codes, &b->d_trace_vals, &b->d_work, &b->d_counter, &b->d_args};
     for(DevBuf *d : bufs) d->release();
     for(int c = 0; c < ALD_NUM_SLOTS; c++) b->d_slabs[c].release();
     b->tx.release(); b->tp.release(); b->d_ts_len.release(); b->d_ts_at.release(); b->d_ts_out.release();
@@ -412,8 +415,30 @@ int ald_batch_upload(ald_batch *b)
     // ONE buffer on the device, its sections filled straight from the batch's host arrays: they live in pinned memory (wire_alloc, hooks
     // installed by ald_batch_create), so every section is one asynchronous copy of the DMA engine and no host thread packs anything
     // (the pack into a second, pinned buffer -- 1.3 GB read and written, 20 ms on sixteen threads -- was as long as the PCIe transfer itself)
-    for(int i = 0; i < HostBatch::S_COUNT; i++)
-        if(b->sec[i].bytes) HIPCHK(hipMemcpyAsync((uint8_t*)b->d_in.p + b->sec[i].off, b->sec[i].src, b->sec[i].bytes, hipMemcpyHostToDevice, us));
+    uint64_t sent = 0, full = 0;
+    for(int i = 0; i < HostBatch::S_COUNT; i++) {
+        full += b->sec[i].bytes;
+        if(!b->sec[i].bytes || b->sec[i].derived) continue;
+        HIPCHK(hipMemcpyAsync((uint8_t*)b->d_in.p + b->sec[i].off, b->sec[i].src, b->sec[i].bytes, hipMemcpyHostToDevice, us));
+        sent += b->sec[i].bytes;
+    }
+    // compact input: what was not copied is derived on the device, on the same stream behind the copies (push_pass waits for that stream)
+    if(b->hb.compact) {
+        const bool log = getenv("ALD_COMPACT_INPUT_LOG") != nullptr && atoi(getenv("ALD_COMPACT_INPUT_LOG")) != 0;
+        if(b->sec[HostBatch::S_SID].derived && n > 0) {
+            if(b->d_gsid.ensure(4 * (size_t)n)) { hipStreamSynchronize(us); return set_err(ALD_ERR_NOMEM, "per-graph sample ids"); }
+            HIPCHK(hipMemcpyAsync(b->d_gsid.p, b->hb.g_sid.data(), 4 * (size_t)n, hipMemcpyHostToDevice, us)); sent += 4ull * n;
+        }
+        if(log) HIPCHK(hipEventRecord(b->ev0, us));
+        { const int rc = ald_expand_input(b, us); if(rc != ALD_OK) { hipStreamSynchronize(us); return rc; } }
+        if(log) {          // one line per upload: how tests and tools/compact_input_rate.py see the mode (the wait is the one upload ends with anyway)
+            float ms = 0; HIPCHK(hipEventRecord(b->ev1, us)); HIPCHK(hipEventSynchronize(b->ev1)); HIPCHK(hipEventElapsedTime(&ms, b->ev0, b->ev1));
+            static const struct { int sec; const char *name; } names[] = {{HostBatch::S_INOFF, "INOFF"}, {HostBatch::S_INEDGE, "INEDGE"}, {HostBatch::S_ESOFF, "ESOFF"}, {HostBatch::S_SID, "SID"}, {HostBatch::S_SABD, "SABD"},
+                                                                         {HostBatch::S_EABD, "EABD"}, {HostBatch::S_ECOUNT, "ECOUNT"}, {HostBatch::S_VTYPE, "VTYPE"}, {HostBatch::S_ESTRAND, "ESTRAND"}};
+            std::string el; for(const auto &x : names) if(b->sec[x.sec].derived) { el += ' '; el += x.name; }
+            fprintf(stderr, "[ald] compact upload: graphs %d elided%s sent %llu full %llu expand_ms %.3f\n", n, el.c_str(), (unsigned long long)sent, (unsigned long long)full, (double)ms);
+        }
+    }
     // outputs
     // a heuristic, not a bound (one graph can need about (E - V + 2) * (V + 14) words): a graph that finds the pool full reports
     // ALD_ST_POOL_FULL and ald_batch_download grows the pool.  ALD_DEBUG_POOL_WORDS starts it small so that tests reach that path.

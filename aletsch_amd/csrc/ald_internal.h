@@ -5,6 +5,7 @@
 #include "host_pack.h"
 #include "record_layout.h"
 #include "../host/transcript_sink.hpp"
+#include <mutex>
 #include <string>
 #include <vector>
 
@@ -133,6 +134,8 @@ struct ald_batch {
     hipEvent_t cdone[ALD_NUM_SLOTS] = {};
     PinBuf pin_in, pin_out, pin_small, pin_index;          // wire buffer / record landing area / status + counters landing area / the result index
     DevBuf d_in, d_status, d_npaths, d_niters, d_pool, d_poolused, d_trace_n, d_trace_codes, d_trace_vals, d_work, d_counter, d_args;
+    DevBuf d_gsid;                                         // compact input with derived sample lists: one sample id per graph (HostBatch::g_sid); not a section of BatchIn
+    std::mutex in_csr_mu;                                  // compact input: a host reader of the in-CSR builds it on first use (HostBatch::ensure_in_csr)
     DevBuf d_index, d_gfirst;                              // result index written by the kernel: index[graph_first[g] + p] = pool offset of record (g, p)
     DevBuf d_pbegin, d_ordoff;                             // the same in (graph, path) order, built on the device on demand (tset_reduce.hip: device_path_table)
     uint64_t index_cap = 0; int64_t total_paths = 0; bool paths_on_device = false;
@@ -176,4 +179,5 @@ struct ald_tset {
 
 unsigned ald_sink_threads(int64_t n_items);          // host threads for a merge of n items (ALD_SINK_THREADS overrides; at most one per table)
 int ald_ensure_index(const ald_batch *b);                 // per-graph index over the record stream of the last download (built on first use)
+int ald_expand_input(const ald_batch *b, hipStream_t st);  // compact input (input_expand.hip): enqueues the kernels that fill the sections b->sec marks derived, behind the copies on st
 int ald_set_err(int code, const std::string &msg);        // sets the calling thread's ald_last_error() text, returns `code`

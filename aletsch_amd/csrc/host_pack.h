@@ -80,9 +80,22 @@ struct HostBatch {
           phasing_offset(wire_alloc<int32_t>(pinned)), phasing_vertex(wire_alloc<int32_t>(pinned)), phasing_count(wire_alloc<int32_t>(pinned)), graph_strand(wire_alloc<char>(pinned)),
           edge_count(wire_alloc<int32_t>(pinned)), edge_rank(wire_alloc<int32_t>(pinned)),
           g_rawdist(wire_alloc<int32_t>(pinned)), off_rp(wire_alloc<int64_t>(pinned)), off_rc(wire_alloc<int64_t>(pinned)),
-          rphase_offset(wire_alloc<int32_t>(pinned)), rphase_coord(wire_alloc<int32_t>(pinned)), rphase_count(wire_alloc<int32_t>(pinned))
+          rphase_offset(wire_alloc<int32_t>(pinned)), rphase_coord(wire_alloc<int32_t>(pinned)), rphase_count(wire_alloc<int32_t>(pinned)),
+          g_sid(wire_alloc<int32_t>(pinned))
     { off_v.assign(1, 0); off_e.assign(1, 0); off_s.assign(1, 0); off_p.assign(1, 0); off_pv.assign(1, 0); off_rp.assign(1, 0); off_rc.assign(1, 0); }
     bool has_raw = false;
+    // ---- compact input (ald_params.reserved & ALD_PARAM_COMPACT_INPUT, or ALD_COMPACT_INPUT=1): columns the device can derive from the
+    // columns that travel are not sent; layout() marks their sections `derived` and input_expand.h fills them after the copies.
+    //   in-CSR             always derived; add does not build it, a host reader asks for it (ensure_in_csr)
+    //   the four defaults  each derived while EVERY graph of the batch left that argument NULL (def_*: "all default so far")
+    //   the sample lists   derived while every edge of every graph has exactly one sample, the same one per graph (g_sid), whose
+    //                      abundance has the bits of the edge's weight (uni_samples)
+    // The def_* flags are kept in either mode (four pointer tests per add call); uni_samples, g_sid and in_built only by a compact batch: the
+    // per-edge test behind uni_samples is work the full upload never did, and with the mode off every path is the one it was.
+    bool compact = false;
+    bool def_eabd = true, def_ecount = true, def_vtype = true, def_estrand = true, uni_samples = true;
+    wvec<int32_t> g_sid;                 // [n] the one sample id of a graph while uni_samples holds (0 for a graph without edges)
+    int in_built = 0;                    // compact: graphs whose in-CSR the host has built (a prefix)
     std::vector<int32_t> cur_, perm_; std::vector<uint8_t> seen_;          // scratch of add_graph, kept across calls
     std::string err;
 
@@ -96,18 +109,20 @@ struct HostBatch {
         vertex_weight.clear(); vertex_lpos.clear(); vertex_rpos.clear(); vertex_type.clear();
         in_offset.clear(); in_edge.clear(); phasing_offset.clear(); phasing_vertex.clear(); phasing_count.clear(); graph_strand.clear(); edge_count.clear(); edge_rank.clear(); has_rank = false;
         g_rawdist.clear(); off_rp.assign(1, 0); off_rc.assign(1, 0); rphase_offset.clear(); rphase_coord.clear(); rphase_count.clear(); has_raw = false;
+        def_eabd = def_ecount = def_vtype = def_estrand = uni_samples = true; g_sid.clear(); in_built = 0;
         err.clear();
     }
 
     // sizes of every array: a rejected graph must leave the batch exactly as it found it (the element-wise path appends while it checks)
-    struct Mark { size_t a[34]; bool has_rank, has_raw; };
+    struct Mark { size_t a[34]; bool has_rank, has_raw; bool def_eabd, def_ecount, def_vtype, def_estrand, uni_samples; };
     Mark mark() const
     {
         Mark m = {{ g_nv.size(), g_ne.size(), g_np.size(), off_v.size(), off_e.size(), off_s.size(), off_p.size(), off_pv.size(),
                     vertex_offset.size(), edge_target.size(), edge_weight.size(), edge_strand.size(), edge_abd.size(), edge_sample_offset.size(), sample_id.size(), sample_abd.size(),
                     vertex_weight.size(), vertex_lpos.size(), vertex_rpos.size(), vertex_type.size(), in_offset.size(), in_edge.size(),
                     phasing_offset.size(), phasing_vertex.size(), phasing_count.size(), graph_strand.size(), edge_count.size(), edge_rank.size(),
-                    g_rawdist.size(), off_rp.size(), off_rc.size(), rphase_offset.size(), rphase_coord.size(), rphase_count.size() }, has_rank, has_raw};
+                    g_rawdist.size(), off_rp.size(), off_rc.size(), rphase_offset.size(), rphase_coord.size(), rphase_count.size() }, has_rank, has_raw,
+                    def_eabd, def_ecount, def_vtype, def_estrand, uni_samples};
         return m;
     }
     void rollback(const Mark &m)
@@ -118,6 +133,45 @@ struct HostBatch {
         in_offset.resize(m.a[20]); in_edge.resize(m.a[21]); phasing_offset.resize(m.a[22]); phasing_vertex.resize(m.a[23]); phasing_count.resize(m.a[24]); graph_strand.resize(m.a[25]);
         edge_count.resize(m.a[26]); edge_rank.resize(m.a[27]); has_rank = m.has_rank;
         g_rawdist.resize(m.a[28]); off_rp.resize(m.a[29]); off_rc.resize(m.a[30]); rphase_offset.resize(m.a[31]); rphase_coord.resize(m.a[32]); rphase_count.resize(m.a[33]); has_raw = m.has_raw;
+        def_eabd = m.def_eabd; def_ecount = m.def_ecount; def_vtype = m.def_vtype; def_estrand = m.def_estrand; uni_samples = m.uni_samples;
+        if(compact) { g_sid.resize(m.a[0]); in_built = std::min(in_built, n()); in_offset.resize((size_t)(off_v[(size_t)in_built] + in_built)); in_edge.resize((size_t)off_e[(size_t)in_built]); }     // what ensure_in_csr had built of the graphs that stay
+    }
+    // the in-CSR of one staged graph: counting sort of edge ids by target; ids ascend within a target == (source, id) order
+    static void in_csr_of(const int32_t *tg, int V, int E, int32_t *io, int32_t *ied, std::vector<int32_t> &cur)
+    {
+        for(int i = 0; i <= V; i++) io[i] = 0;
+        for(int k = 0; k < E; k++) io[tg[k] + 1]++;
+        for(int i = 0; i < V; i++) io[i + 1] += io[i];
+        cur.assign(io, io + V);
+        for(int k = 0; k < E; k++) ied[cur[tg[k]]++] = k;
+    }
+    // compact: in_offset / in_edge of every graph of the batch, for a host reader (add did not build them).  Nothing to do otherwise.
+    void ensure_in_csr()
+    {
+        if(!compact || in_built == n()) return;
+        in_offset.resize(vertex_offset.size()); in_edge.resize(edge_target.size());
+        for(int g = in_built; g < n(); g++) in_csr_of(edge_target.data() + off_e[g], g_nv[g], g_ne[g], &in_offset[(size_t)(off_v[g] + g)], in_edge.data() + off_e[g], cur_);
+        in_built = n();
+    }
+    // a raw graph must not have parallel edges into the sink: rows are sorted by target, so they would end one row
+    bool parallel_into_sink(int g) const
+    {
+        const int V = g_nv[g]; const int64_t oe = off_e[g], ovo = off_v[g] + g;
+        for(int s = 0; s + 1 < V; s++) { const int a = vertex_offset[ovo + s], b = vertex_offset[ovo + s + 1]; if(b - a >= 2 && edge_target[oe + b - 1] == V - 1 && edge_target[oe + b - 2] == V - 1) return true; }
+        return false;
+    }
+    // does the staged graph keep the sample lists derivable?  eo / so / eb: its first entry in edge_sample_offset / sample_id / edge_target
+    void note_samples(size_t eo, size_t so, size_t eb, int E)
+    {
+        if(!compact) return;
+        int32_t sid0 = 0;
+        if(uni_samples) {
+            if(edge_sample_offset[eo] != 0) uni_samples = false;
+            for(int k = 0; k < E && uni_samples; k++)
+                if(edge_sample_offset[eo + k + 1] != k + 1 || sample_id[so + k] != sample_id[so] || memcmp(&sample_abd[so + k], &edge_weight[eb + k], 8) != 0) uni_samples = false;
+            if(uni_samples && E > 0) sid0 = sample_id[so];
+        }
+        g_sid.push_back(sid0);
     }
     // the first graph that brings a creation rank turns the column on: every edge staged before it gets its CSR position
     void enable_rank()
@@ -161,7 +215,8 @@ struct HostBatch {
             if(!sorted) std::stable_sort(perm.begin() + a, perm.begin() + b, [&](int x, int y) { return g.edge_target[x] != g.edge_target[y] ? g.edge_target[x] < g.edge_target[y] : (rk ? rk[x] < rk[y] : false); });
         }
         if(rk) enable_rank();
-        size_t e0 = edge_target.size(), s0 = sample_id.size();
+        size_t e0 = edge_target.size(), s0 = sample_id.size(); const size_t eo0 = edge_sample_offset.size();
+        def_eabd = def_eabd && !g.edge_abd; def_ecount = def_ecount && !g.edge_count; def_vtype = def_vtype && !g.vertex_type; def_estrand = def_estrand && !g.edge_strand;
         // canonical input (rows sorted, sample lists ascending, strands in range: what the reference's containers produce) is appended
         // by ranges; anything else goes through the element-wise path below, which sorts and reports defects
         bool canonical = true;
@@ -207,6 +262,7 @@ struct HostBatch {
                 std::sort(t.begin(), t.end());
                 for(size_t j = 1; j < t.size(); j++) if(t[j].first == t[j - 1].first) { err = "duplicate sample id on an edge"; return ALD_ERR_INVALID; }
                 for(size_t j = 0; j < t.size(); j++) { sample_id[base + j] = t[j].first; sample_abd[base + j] = t[j].second; }
+                def_eabd = false;             // the default sum above ran in the caller's order, the staged list is sorted: the device could not repeat it
             }
             edge_abd.push_back(g.edge_abd ? g.edge_abd[q] : sum);
             if(g.edge_count && g.edge_count[q] < 0) { err = "negative edge count"; return ALD_ERR_INVALID; }
@@ -215,16 +271,13 @@ struct HostBatch {
             edge_sample_offset.push_back((int32_t)(sample_id.size() - s0));
         }
         }
+        note_samples(eo0, s0, e0, E);
         vertex_offset.insert(vertex_offset.end(), g.vertex_offset, g.vertex_offset + V + 1);
         // ---- in-CSR: counting sort of edge ids by target; ids ascend within a target == (source, id) order ----
-        {
+        if(!compact) {
             size_t b0 = in_offset.size(); in_offset.resize(b0 + V + 1, 0);
-            int32_t *io = in_offset.data() + b0;
-            for(int k = 0; k < E; k++) io[edge_target[e0 + k] + 1]++;
-            for(int i = 0; i < V; i++) io[i + 1] += io[i];
             size_t ie0 = in_edge.size(); in_edge.resize(ie0 + E);
-            cur_.assign(io, io + V);
-            for(int k = 0; k < E; k++) in_edge[ie0 + cur_[edge_target[e0 + k]]++] = k;
+            in_csr_of(edge_target.data() + e0, V, E, in_offset.data() + b0, in_edge.data() + ie0, cur_);
         }
         vertex_weight.insert(vertex_weight.end(), g.vertex_weight, g.vertex_weight + V); vertex_lpos.insert(vertex_lpos.end(), g.vertex_lpos, g.vertex_lpos + V); vertex_rpos.insert(vertex_rpos.end(), g.vertex_rpos, g.vertex_rpos + V);
         if(g.vertex_type) vertex_type.insert(vertex_type.end(), g.vertex_type, g.vertex_type + V); else vertex_type.resize(vertex_type.size() + V, -1);
@@ -271,8 +324,8 @@ struct HostBatch {
         const int gi = n() - 1, V = g_nv[gi], E = g_ne[gi]; const int64_t oe = off_e[gi], ovo = off_v[gi] + gi;
         // parallel edges out of the source / into the sink: the rows are sorted by target, the in-CSR by source
         for(int k = vertex_offset[ovo] + 1; k < vertex_offset[ovo + 1]; k++) if(edge_target[oe + k] == edge_target[oe + k - 1]) { rollback(m); err = "parallel edges out of the source: the reference's boundary grouping is undefined on them"; return ALD_ERR_INVALID; }
-        { int last = -1; for(int k = in_offset[ovo + V - 1]; k < in_offset[ovo + V]; k++) { const int e = in_edge[oe + k]; int s = 0; while(vertex_offset[ovo + s + 1] <= e) s++; if(s == last) { rollback(m); err = "parallel edges into the sink: the reference's boundary grouping is undefined on them"; return ALD_ERR_INVALID; } last = s; } }
-        (void)E;
+        if(parallel_into_sink(gi)) { rollback(m); err = "parallel edges into the sink: the reference's boundary grouping is undefined on them"; return ALD_ERR_INVALID; }
+        (void)E; (void)V;
         g_rawdist[(size_t)gi] = max_group_boundary_distance; has_raw = true;
         const size_t c0 = rphase_coord.size();
         for(int p = 0; p < P; p++) { for(int k = ph->phase_offset[p]; k < ph->phase_offset[p + 1]; k++) rphase_coord.push_back(ph->phase_coord[k]); rphase_offset.push_back((int32_t)(rphase_coord.size() - c0)); rphase_count.push_back(ph->phase_count[p]); }
@@ -348,8 +401,12 @@ struct HostBatch {
         { const int64_t rp = off_rp.back(), rc = off_rc.back(); g_rawdist.resize(n0 + n); off_rp.resize(n0 + n + 1); off_rc.resize(n0 + n + 1); const size_t r0 = rphase_offset.size(); rphase_offset.resize(r0 + n);
           for(int i = 0; i < n; i++) { g_rawdist[n0 + i] = -1; off_rp[n0 + i + 1] = rp; off_rc[n0 + i + 1] = rc; rphase_offset[r0 + i] = 0; } }
         for(int i = 0; i < n; i++) { off_v[n0 + i + 1] = off_v[n0] + iv[i + 1]; off_e[n0 + i + 1] = off_e[n0] + ie[i + 1]; off_s[n0 + i + 1] = off_s[n0] + is[i + 1]; off_p[n0 + i + 1] = off_p[n0] + ip[i + 1]; off_pv[n0 + i + 1] = off_pv[n0] + ipv[i + 1]; }
-        vertex_offset.resize(vo0 + TV + n); in_offset.resize(vo0 + TV + n);
-        edge_target.resize(e0 + TE); edge_weight.resize(e0 + TE); edge_strand.resize(e0 + TE); edge_abd.resize(e0 + TE); edge_count.resize(e0 + TE); in_edge.resize(e0 + TE); if(has_rank) edge_rank.resize(e0 + TE);
+        vertex_offset.resize(vo0 + TV + n); if(!compact) in_offset.resize(vo0 + TV + n);
+        edge_target.resize(e0 + TE); edge_weight.resize(e0 + TE); edge_strand.resize(e0 + TE); edge_abd.resize(e0 + TE); edge_count.resize(e0 + TE); if(!compact) in_edge.resize(e0 + TE); if(has_rank) edge_rank.resize(e0 + TE);
+        if(compact) g_sid.resize(n0 + n);
+        def_eabd = def_eabd && !eabd; def_ecount = def_ecount && !ecount; def_vtype = def_vtype && !vtype; def_estrand = def_estrand && !estrand;
+        const bool uni0 = compact && uni_samples;      // still worth testing?  (never by a batch that uploads everything)
+        std::vector<int> mixed(nthr, 0);             // some graph of the slice has sample lists the device could not derive
         edge_sample_offset.resize(eo0 + TE + n); sample_id.resize(s0 + TS); sample_abd.resize(s0 + TS);
         vertex_weight.resize(v0 + TV); vertex_lpos.resize(v0 + TV); vertex_rpos.resize(v0 + TV); vertex_type.resize(v0 + TV);
         phasing_offset.resize(po0 + TP + n); phasing_vertex.resize(pv0 + TPV); phasing_count.resize(p0 + TP);
@@ -369,8 +426,10 @@ struct HostBatch {
                 }
                 if(erank && worst < 2 && E > 0 && !rank_is_permutation(erank + ie[g], E, seen)) { worst = 2; break; }
                 if(erank && !permuted[t]) for(int k = 0; k < E; k++) if(erank[ie[g] + k] != k) { permuted[t] = 1; break; }
+                bool uni = uni0 && !mixed[t] && so[0] == 0;
                 for(int k = 0; k < E && worst < 2; k++) {
                     if(so[k + 1] < so[k]) { worst = 2; break; }
+                    if(uni && (so[k + 1] != k + 1 || sid[is[g] + k] != sid[is[g]] || memcmp(&sabd[is[g] + k], &ew[ie[g] + k], 8) != 0)) uni = false;
                     if(estrand && estrand[ie[g] + k] > 2) { worst = 2; break; }
                     if(ecount && ecount[ie[g] + k] < 0) { worst = 2; break; }
                     for(int j = so[k] + 1; j < so[k + 1]; j++) if(sid[is[g] + j - 1] >= sid[is[g] + j]) worst = 1;
@@ -385,6 +444,7 @@ struct HostBatch {
                     }
                 }
                 if(worst) break;                                    // the batch is rolled back: nothing more to stage here
+                if(compact) { if(!uni) mixed[t] = 1; g_sid[n0 + g] = (uni && E > 0) ? sid[is[g]] : 0; }
                 // ---- the copy: graph g to its place ----
                 const int64_t a_v = iv[g], a_e = ie[g], a_s = is[g], a_p = ip[g], a_pv = ipv[g]; const int64_t NS = is[g + 1] - a_s, NPV = ipv[g + 1] - a_pv;
                 memcpy(&vertex_offset[vo0 + a_v + g], vo, 4 * ((size_t)V + 1));
@@ -406,12 +466,7 @@ struct HostBatch {
                 if(!eabd) for(int k = 0; k < E; k++) { double sum = 0; for(int j = so[k]; j < so[k + 1]; j++) sum += sabd[is[g] + j]; edge_abd[e0 + ie[g] + k] = sum; }
                 if(!ecount) for(int k = 0; k < E; k++) edge_count[e0 + ie[g] + k] = so[k + 1] - so[k];
                 if(has_rank && !erank) for(int k = 0; k < E; k++) edge_rank[e0 + ie[g] + k] = k;
-                int32_t *io = &in_offset[vo0 + iv[g] + g]; int32_t *ied = E > 0 ? &in_edge[e0 + ie[g]] : nullptr;
-                for(int i = 0; i <= V; i++) io[i] = 0;
-                for(int k = 0; k < E; k++) io[tg[k] + 1]++;
-                for(int i = 0; i < V; i++) io[i + 1] += io[i];
-                cur.assign(io, io + V);
-                for(int k = 0; k < E; k++) ied[cur[tg[k]]++] = k;
+                if(!compact) in_csr_of(tg, V, E, &in_offset[vo0 + iv[g] + g], E > 0 ? &in_edge[e0 + ie[g]] : nullptr, cur);
             }
             verdict[t] = worst;
         };
@@ -421,6 +476,7 @@ struct HostBatch {
             rollback(m0);
             return add_packed_serial(n, nv, ne, np, voff, etgt, ew, estrand, eabd, esoff, sid, sabd, vw, lpos, rpos, vtype, poff, pv, pc, gstrand, ecount, erank);
         }
+        for(unsigned t = 0; t < nthr; t++) if(mixed[t]) uni_samples = false;
         if(erank && !m0.has_rank) { bool any = false; for(unsigned t = 0; t < nthr; t++) any = any || permuted[t]; if(!any) { edge_rank.clear(); has_rank = false; } }     // identity everywhere: nothing to carry
         return ALD_OK;
     }
@@ -456,7 +512,7 @@ struct HostBatch {
             int worst = 0;
             for(int i = (int)((int64_t)n * t / nthr); i < (int)((int64_t)n * (t + 1) / nthr) && !worst; i++) {
                 if(raw_dist[i] < 0) continue;
-                const size_t g = n0 + (size_t)i; const int V = g_nv[g]; const int64_t oe = off_e[g], ovo = off_v[g] + (int64_t)g;
+                const size_t g = n0 + (size_t)i; const int64_t oe = off_e[g], ovo = off_v[g] + (int64_t)g;
                 if(g_np[g] != 0) { worst = 1; break; }
                 const int P = (int)(ip[(size_t)i + 1] - ip[(size_t)i]); const int32_t *po = rpoff ? rpoff + ip[(size_t)i] + i : nullptr;
                 if(P > 0 && po[0] != 0) { worst = 2; break; }
@@ -464,8 +520,7 @@ struct HostBatch {
                 if(worst) break;
                 for(int k = vertex_offset[ovo] + 1; k < vertex_offset[ovo + 1]; k++) if(edge_target[oe + k] == edge_target[oe + k - 1]) { worst = 3; break; }
                 if(worst) break;
-                int s = 0, last = -1;
-                for(int k = in_offset[ovo + V - 1]; k < in_offset[ovo + V]; k++) { const int e = in_edge[oe + k]; while(vertex_offset[ovo + s + 1] <= e) s++; if(s == last) { worst = 4; break; } last = s; }   // in-CSR ids ascend: so do their sources
+                if(parallel_into_sink((int)g)) worst = 4;
             }
             verdict[t] = worst;
         });
@@ -498,13 +553,14 @@ struct HostBatch {
     }
 
     // ---- one contiguous buffer; section offsets are 256-byte aligned ----
-    struct Section { const void *src; uint64_t bytes; uint64_t off; };
+    // derived: the section is reserved in the buffer like any other but nothing is copied into it -- the device fills it (compact input)
+    struct Section { const void *src; uint64_t bytes; uint64_t off; bool derived; };
     enum { S_NV, S_NE, S_NP, S_OFFV, S_OFFE, S_OFFS, S_OFFP, S_OFFPV, S_VOFF, S_ETGT, S_EW, S_ESTRAND, S_EABD, S_ESOFF, S_SID, S_SABD,
            S_VW, S_LPOS, S_RPOS, S_VTYPE, S_INOFF, S_INEDGE, S_POFF, S_PV, S_PC, S_GSTRAND, S_ECOUNT, S_ERANK,
            S_RAWDIST, S_OFFRP, S_OFFRC, S_RPOFF, S_RPCOORD, S_RPCOUNT, S_COUNT };
     uint64_t layout(Section sec[S_COUNT]) const
     {
-        auto set = [&](int i, const void *p, uint64_t b) { sec[i].src = p; sec[i].bytes = b; };
+        auto set = [&](int i, const void *p, uint64_t b) { sec[i].src = p; sec[i].bytes = b; sec[i].derived = false; };
         set(S_NV, g_nv.data(), 4ull * g_nv.size()); set(S_NE, g_ne.data(), 4ull * g_ne.size()); set(S_NP, g_np.data(), 4ull * g_np.size());
         set(S_OFFV, off_v.data(), 8ull * off_v.size()); set(S_OFFE, off_e.data(), 8ull * off_e.size()); set(S_OFFS, off_s.data(), 8ull * off_s.size());
         set(S_OFFP, off_p.data(), 8ull * off_p.size()); set(S_OFFPV, off_pv.data(), 8ull * off_pv.size());
@@ -518,6 +574,15 @@ struct HostBatch {
         set(S_ERANK, edge_rank.data(), has_rank ? 4ull * edge_rank.size() : 0);      // travels only when some caller supplied a creation rank
         set(S_RAWDIST, g_rawdist.data(), has_raw ? 4ull * g_rawdist.size() : 0); set(S_OFFRP, off_rp.data(), has_raw ? 8ull * off_rp.size() : 0); set(S_OFFRC, off_rc.data(), has_raw ? 8ull * off_rc.size() : 0);
         set(S_RPOFF, rphase_offset.data(), has_raw ? 4ull * rphase_offset.size() : 0); set(S_RPCOORD, rphase_coord.data(), has_raw ? 4ull * rphase_coord.size() : 0); set(S_RPCOUNT, rphase_count.data(), has_raw ? 4ull * rphase_count.size() : 0);
+        if(compact) {
+            auto derive = [&](int i, uint64_t b) { sec[i].src = nullptr; sec[i].bytes = b; sec[i].derived = true; };
+            derive(S_INOFF, 4ull * vertex_offset.size()); derive(S_INEDGE, 4ull * edge_target.size());      // the sizes add would have given them
+            if(def_eabd) derive(S_EABD, sec[S_EABD].bytes);
+            if(def_ecount) derive(S_ECOUNT, sec[S_ECOUNT].bytes);
+            if(def_vtype) derive(S_VTYPE, sec[S_VTYPE].bytes);
+            if(def_estrand) derive(S_ESTRAND, sec[S_ESTRAND].bytes);
+            if(uni_samples) { derive(S_ESOFF, sec[S_ESOFF].bytes); derive(S_SID, sec[S_SID].bytes); derive(S_SABD, sec[S_SABD].bytes); }
+        }
         uint64_t o = 0;
         for(int i = 0; i < S_COUNT; i++) { sec[i].off = o; o = (o + sec[i].bytes + 255) / 256 * 256; }
         return o < 256 ? 256 : o;
@@ -531,7 +596,7 @@ struct HostBatch {
         Piece pc[S_COUNT]; int np = 0; uint64_t tot = 0;
         for(int i = 0; i < S_COUNT; i++) {
             const uint64_t a = std::max<uint64_t>(lo, sec[i].off), b = std::min<uint64_t>(hi, sec[i].off + sec[i].bytes);
-            if(!sec[i].bytes || b <= a) continue;
+            if(!sec[i].bytes || sec[i].derived || b <= a) continue;
             pc[np++] = Piece{a, (const uint8_t*)sec[i].src + (a - sec[i].off), b - a}; tot += b - a;
         }
         if(!tot) return;
@@ -682,6 +747,14 @@ static inline void params_from_abi(const ald_params *p, Params &q)
     if(!p) { const double r[8] = {0.30, 0.00, 1.10, 1.10, 0.75, 0.30, 0.00, 1.00}; for(int i = 0; i < 8; i++) d.max_decompose_error_ratio[i] = r[i]; d.min_guaranteed_edge_weight = 0.01; d.min_transcript_coverage = 2.0; d.max_num_exons = 10000; d.reserved = 0; p = &d; }
     for(int i = 0; i < 8; i++) q.max_ratio[i] = p->max_decompose_error_ratio[i];
     q.min_w = p->min_guaranteed_edge_weight; q.min_cov = p->min_transcript_coverage; q.max_num_exons = p->max_num_exons; q.pad = 0;
+}
+
+// compact input: which sections the device derives, from HostBatch::layout's `derived` marks (the in-CSR and the sample lists go as one each)
+enum { ALD_DERIVE_INCSR = 1, ALD_DERIVE_SAMPLES = 2, ALD_DERIVE_EABD = 4, ALD_DERIVE_ECOUNT = 8, ALD_DERIVE_VTYPE = 16, ALD_DERIVE_ESTRAND = 32 };
+inline unsigned derive_mask(const HostBatch::Section sec[HostBatch::S_COUNT])
+{
+    return (sec[HostBatch::S_INOFF].derived ? ALD_DERIVE_INCSR : 0) | (sec[HostBatch::S_ESOFF].derived ? ALD_DERIVE_SAMPLES : 0) | (sec[HostBatch::S_EABD].derived ? ALD_DERIVE_EABD : 0)
+         | (sec[HostBatch::S_ECOUNT].derived ? ALD_DERIVE_ECOUNT : 0) | (sec[HostBatch::S_VTYPE].derived ? ALD_DERIVE_VTYPE : 0) | (sec[HostBatch::S_ESTRAND].derived ? ALD_DERIVE_ESTRAND : 0);
 }
 
 } // namespace ald

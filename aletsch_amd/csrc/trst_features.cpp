@@ -73,6 +73,7 @@ int ald_batch_features(const ald_batch *b, int32_t graph, const ald_graph_extras
         if(rc2 != ALD_OK) return ald_set_err(rc2, staged_copy.err);
         gi = 0;
     }
+    if(b->hb.compact && b->hb.g_rawdist[(size_t)graph] < 0) { ald_batch *bm = const_cast<ald_batch*>(b); std::lock_guard<std::mutex> lk(bm->in_csr_mu); bm->hb.ensure_in_csr(); }      // in_weights() below reads the in-CSR, which a compact batch did not build at add
     const GraphRO G(gi == graph && b->hb.g_rawdist[(size_t)graph] < 0 ? b->hb : staged_copy, gi);
     const int64_t p0 = b->res.path_begin[graph]; const int np = (int)(b->res.path_begin[graph + 1] - p0);
     std::vector<std::vector<Junc>> junc((size_t)np);

@@ -128,13 +128,17 @@ staged_graph stage_raw(SpliceGraph &gx, const PhaseSet &px, int max_group_bounda
     return out;
 }
 
+// compact input (ALD_PARAM_COMPACT_INPUT): a configuration that has a `compact_input` member switches it on with it; the reference's own
+// parameters class has none and keeps the full upload
+template<class Parameters> auto compact_input_of(const Parameters &cfg, int) -> decltype((bool)cfg.compact_input) { return (bool)cfg.compact_input; }
+template<class Parameters> bool compact_input_of(const Parameters &, long) { return false; }
 template<class Parameters>
 ald_params stage_params(const Parameters &cfg)
 {
     ald_params p;
     for(int i = 0; i < 8; i++) p.max_decompose_error_ratio[i] = cfg.max_decompose_error_ratio[i];
     p.min_guaranteed_edge_weight = cfg.min_guaranteed_edge_weight; p.min_transcript_coverage = cfg.min_transcript_coverage;
-    p.max_num_exons = cfg.max_num_exons; p.reserved = 0;
+    p.max_num_exons = cfg.max_num_exons; p.reserved = compact_input_of(cfg, 0) ? ALD_PARAM_COMPACT_INPUT : 0;
     return p;
 }
 

@@ -29,6 +29,11 @@ class AldParams(C.Structure):
                 ("min_transcript_coverage", C.c_double), ("max_num_exons", C.c_int32), ("reserved", C.c_int32)]
 
 
+# ald_params.reserved, bit 0 (ALD_PARAM_COMPACT_INPUT): columns of a batch that follow from its other columns are derived on the device
+# instead of copied to it.  p = default_params(); p.reserved |= PARAM_COMPACT_INPUT; DecompBatch(0, p) / decompose(pg, 0, p)
+PARAM_COMPACT_INPUT = 1
+
+
 class SynthSpec(C.Structure):
     _fields_ = [("seed", C.c_uint64), ("n_graphs", C.c_int32), ("v_min", C.c_int32), ("v_max", C.c_int32),
                 ("edges_per_vertex", C.c_int32), ("fixed_edges", C.c_int32), ("weight_mode", C.c_int32),
@@ -359,8 +364,19 @@ class DecompBatch:
     def clear(self):
         _check(self._lib.ald_batch_clear(self._h))
 
-    def add(self, pg: PackedGraphs):
-        _check(self._lib.ald_batch_add_packed(self._h, *pg.c_args()))
+    _OMITTABLE = ("edge_strand", "edge_abd", "vertex_type", "edge_count", "edge_rank")     # the columns ald_batch_add_packed takes as NULL
+
+    def add(self, pg: PackedGraphs, omit=()):
+        """ald_batch_add_packed.  omit: names of optional columns handed over as NULL although `pg` has them, so that they take their
+        defaults (edge_strand 0, edge_abd the sum of the edge's sample abundances, vertex_type -1, edge_count the number of samples,
+        edge_rank the CSR position) -- and, under PARAM_COMPACT_INPUT, stay off the wire."""
+        args = list(pg.c_args())
+        assert len(args) == len(PackedGraphs.C_ARG_NAMES)
+        for name in omit:
+            if name not in self._OMITTABLE:
+                raise ValueError(f"DecompBatch.add: {name!r} cannot be omitted (optional columns: {', '.join(self._OMITTABLE)})")
+            args[PackedGraphs.C_ARG_NAMES.index(name)] = None
+        _check(self._lib.ald_batch_add_packed(self._h, *args))
 
     def add_packed_raw(self, pg: PackedGraphs, max_group_boundary_distance: int = 10000, phases=None):
         """every graph of `pg` as a RAW graph (pre-steps on the device): ald_batch_add_packed_raw; phases: per graph a list of

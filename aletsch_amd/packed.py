@@ -59,8 +59,12 @@ class PackedGraphs:
         E = self.g_ne.astype(np.int64)
         return (np.arange(int(E.sum()), dtype=np.int64) - np.repeat(np.concatenate([[0], np.cumsum(E)[:-1]]), E)).astype(np.int32)
 
+    # the argument order shared by ald_batch_add_packed / ora_run_packed: what c_args() returns, name by name
+    C_ARG_NAMES = ("n", "g_nv", "g_ne", "g_np", "vertex_offset", "edge_target", "edge_weight", "edge_strand", "edge_abd", "edge_sample_offset", "sample_id", "sample_abd",
+                   "vertex_weight", "vertex_lpos", "vertex_rpos", "vertex_type", "phasing_offset", "phasing_vertex", "phasing_count", "graph_strand", "edge_count", "edge_rank")
+
     def c_args(self):
-        """Pointers in the argument order shared by ald_batch_add_packed / ora_run_packed."""
+        """Pointers in the argument order shared by ald_batch_add_packed / ora_run_packed (C_ARG_NAMES)."""
         def p(a, t):
             return a.ctypes.data_as(C.POINTER(t))
         return (

@@ -68,8 +68,13 @@ typedef struct ald_params {
     double  min_guaranteed_edge_weight;   /* 0.01 */
     double  min_transcript_coverage;      /* 2.0  */
     int32_t max_num_exons;                /* 10000 */
-    int32_t reserved;
+    int32_t reserved;                     /* bit 0: ALD_PARAM_COMPACT_INPUT; every other bit is ignored */
 } ald_params;
+/* Compact input (off by default): columns of a batch that follow from its other columns are not copied to the device but derived
+ * there after the upload -- the in-CSR always; edge_abd, edge_count, vertex_type and edge_strand each while every graph of the batch
+ * left it NULL; the sample lists while every edge has one sample, the same one per graph, with the edge's weight as its abundance.
+ * Results are those of a full upload, bit for bit.  The environment variable ALD_COMPACT_INPUT=1 / 0 forces the mode on / off. */
+#define ALD_PARAM_COMPACT_INPUT 1
 
 /* One splice graph, caller-owned arrays, borrowed for the duration of the call.
  * Vertex 0 is the source, vertex V-1 the sink (reference rnacore/splice_graph.h).
