@@ -30,11 +30,14 @@ ALD_FOR_EACH_CLASS(ALD_DECL)
 #define ALD_TWIN_SPILL_DEFAULT(q, sz, cap) ((q) == 0 ? (int64_t)1 << 40 : (int64_t)0)
 namespace {
 
-// A batch owns seven HIP streams and a pipelined caller keeps several batches in flight; the ROCm runtime maps all streams of a process
-// onto FOUR hardware queues by default, so the D2H copy of batch k regularly sat in the same queue as the kernel of batch k + 1 and
-// waited for it (download 24-38 ms instead of 3 ms per step).  The runtime reads GPU_MAX_HW_QUEUES when it initialises, so the library
-// sets it -- unless the caller did -- when it is LOADED: before any HIP call of its own, and before the first HIP call of a program
-// that links it.  (A process that initialised HIP before it dlopen()ed the library keeps what it had)
+// A batch owns seven normal-priority HIP streams and a pipelined caller keeps several batches in flight; the ROCm runtime maps the streams
+// of one priority class onto FOUR in-order hardware queues by default, so a D2H copy of batch k on the batch's own stream regularly sat
+// in the same queue as the kernel of batch k + 1 and waited for it (download 24-38 ms instead of 3 ms per step).  The pipeline no longer
+// depends on the queue count: uploads and downloads travel on streams of other priority classes (ald_internal.h: up_stream, dl_stream),
+// and what is left on the normal-priority queues -- memsets, kernels, events -- is ordered by the caller anyway.  The default below stays
+// as a courtesy to mixed batches (six side streams per batch): the runtime reads GPU_MAX_HW_QUEUES when it initialises, so the library
+// sets it -- unless the caller did -- when it is LOADED.  (A process that initialised HIP before it dlopen()ed the library, or whose
+// operator exported another value, keeps what it had)
 __attribute__((constructor)) void ald_default_hw_queues() { setenv("GPU_MAX_HW_QUEUES", "8", 0); }
 
 thread_local std::string g_err;
@@ -278,6 +281,27 @@ std::atomic<int> g_live_batches{0};
 void *wire_pinned_alloc(size_t bytes) { return pinned_cache().get(bytes ? bytes : 1); }
 void wire_pinned_release(void *p) { pinned_cache().put(p); }
 struct WireHooksInstaller { WireHooksInstaller() { wire_hooks().alloc = wire_pinned_alloc; wire_hooks().release = wire_pinned_release; } } g_wire_hooks_installer;
+
+// ALD_DOWNLOAD_STREAM=2: the ONE download stream of a device, in the highest priority class, shared by its batches (a stream per batch
+// there would share a hardware queue with some batch's up_stream and could queue behind 25 ms of input copies).  Counted: the last batch
+// of the device to go destroys it.
+struct SharedDownloadStreams {
+    std::mutex m;
+    std::map<int, std::pair<hipStream_t, int>> by_device;      // device -> stream, batches holding it
+    hipStream_t get(int device, int priority) {
+        std::lock_guard<std::mutex> lk(m);
+        auto &e = by_device[device];
+        if(!e.first && hipStreamCreateWithPriority(&e.first, hipStreamNonBlocking, priority) != hipSuccess) { by_device.erase(device); return nullptr; }
+        e.second++; return e.first;
+    }
+    void put(int device) {
+        std::lock_guard<std::mutex> lk(m);
+        auto it = by_device.find(device);
+        if(it == by_device.end() || --it->second.second > 0) return;
+        hipStreamSynchronize(it->second.first); hipStreamDestroy(it->second.first); by_device.erase(it);
+    }
+};
+SharedDownloadStreams &shared_download_streams() { static SharedDownloadStreams *s = new SharedDownloadStreams(); return *s; }
 }
 
 int ald_batch_create(const ald_params *p, int device, ald_batch **out)
@@ -300,12 +324,23 @@ int ald_batch_create(const ald_params *p, int device, ald_batch **out)
     if(const char *ev = getenv("ALD_SIDE_STREAMS")) { const int k = atoi(ev); if(k >= 1 && k <= ALD_SIDE_STREAMS_MAX) b->n_cstream = k; }      // tuning knob
     for(int q = 0; q < b->n_cstream && ok; q++) ok = hipStreamCreateWithFlags(&b->cstream[q], hipStreamNonBlocking) == hipSuccess;
     const int up_mode = getenv("ALD_UPLOAD_STREAM") ? atoi(getenv("ALD_UPLOAD_STREAM")) : 2;      // 0: uploads through the batch's own stream (A/B); 1: a stream of the lowest priority; 2: of the highest (default: DMA copies take nothing from a kernel, and they finish sooner: 24 against 31 ms per 1.35 GB batch)
-    if(ok && up_mode != 0) {
+    // 0: results through the batch's own stream (A/B); 1: a stream per batch in the lowest class, which nothing else uses (A/B: with four
+    // queues one batch object in four still waited most of a kernel there); 2 (default): one stream per device in the highest class, the
+    // uploads' (ald_internal.h: dl_stream; DESIGN.md section 5 has the numbers).  Priority 0 is the class of `stream` and the side streams.
+    const int dl_mode = getenv("ALD_DOWNLOAD_STREAM") ? atoi(getenv("ALD_DOWNLOAD_STREAM")) : 2;
+    if(ok && (up_mode != 0 || dl_mode != 0)) {
         int least = 0, greatest = 0;
         if(hipDeviceGetStreamPriorityRange(&least, &greatest) == hipSuccess && least != greatest) {
-            if(hipStreamCreateWithPriority(&b->up_stream, hipStreamNonBlocking, up_mode == 2 ? greatest : least) != hipSuccess) b->up_stream = nullptr;      // (without it: the batch's stream, as before)
+            if(up_mode != 0 && hipStreamCreateWithPriority(&b->up_stream, hipStreamNonBlocking, up_mode == 2 ? greatest : least) != hipSuccess) b->up_stream = nullptr;      // (without it: the batch's stream, as before)
+            if(dl_mode == 2 && greatest != 0) {
+                b->dl_stream = shared_download_streams().get(device, greatest);
+                b->dl_shared = b->dl_stream && hipEventCreateWithFlags(&b->dl_done, hipEventDisableTiming) == hipSuccess;
+                if(b->dl_stream && !b->dl_shared) { shared_download_streams().put(device); b->dl_stream = nullptr; }
+            }
+            else if(dl_mode != 0 && least != 0 && hipStreamCreateWithPriority(&b->dl_stream, hipStreamNonBlocking, least) != hipSuccess) b->dl_stream = nullptr;
         }
     }
+    if(!b->dl_stream) b->dl_stream = b->stream;            // as up_stream: without a second priority class the results travel as before
     for(int c = 0; c < ALD_NUM_SLOTS && ok; c++) ok = hipEventCreateWithFlags(&b->cdone[c], hipEventDisableTiming) == hipSuccess;
     if(!ok) { ald_batch_destroy(b); return set_err(ALD_ERR_HIP, "stream/event creation failed"); }
     *out = b;
@@ -317,6 +352,9 @@ int ald_batch_destroy(ald_batch *b)
     if(!b) return ALD_OK;
     hipSetDevice(b->device);
     if(b->stream) hipStreamSynchronize(b->stream);
+    // (a download that failed half way may have left copies into the pinned buffers behind; the shared stream carries other batches' too)
+    if(b->dl_shared) { if(hipEventRecord(b->dl_done, b->dl_stream) == hipSuccess) hipEventSynchronize(b->dl_done); }
+    else if(b->dl_stream && b->dl_stream != b->stream) hipStreamSynchronize(b->dl_stream);
     b->pin_in.release(); b->pin_out.release(); b->pin_small.release(); b->pin_index.release(); delete b->pass0; b->pass0 = nullptr;
     DevBuf *bufs[] = {&b->d_in, &b->d_gsid, &b->d_status, &b->d_npaths, &b->d_niters, &b->d_pool, &b->d_poolused, &b->d_index, &b->d_gfirst, &b->d_pbegin, &b->d_ordoff, &b->d_trace_n, &b->d_trace_codes, &b->d_trace_vals, &b->d_work, &b->d_counter, &b->d_args};
     for(DevBuf *d : bufs) d->release();
@@ -328,6 +366,8 @@ int ald_batch_destroy(ald_batch *b)
     if(b->ev0) hipEventDestroy(b->ev0);
     if(b->ev1) hipEventDestroy(b->ev1);
     if(b->up_stream) { hipStreamSynchronize(b->up_stream); hipStreamDestroy(b->up_stream); }
+    if(b->dl_shared) { hipEventDestroy(b->dl_done); shared_download_streams().put(b->device); }
+    else if(b->dl_stream && b->dl_stream != b->stream) hipStreamDestroy(b->dl_stream);
     if(b->stream) hipStreamDestroy(b->stream);
     delete b;
     if(g_live_batches.fetch_sub(1) == 1) pinned_cache().drop_all();      // the last batch of the process: the kept pinned blocks go back
@@ -570,11 +610,24 @@ typedef std::chrono::steady_clock::time_point ald_tp;
 double ms_between(ald_tp a, ald_tp c) { return std::chrono::duration<double, std::milli>(c - a).count(); }
 struct EndStamps { ald_tp P1, P2; int64_t bytes = 0; };      // the kernels of pass 0 are through / its status words are here; bytes moved to the host
 
+// the batch's result copies on dl_stream are on the host.  A stream shared with other batches is never waited for as a whole: their
+// copies, issued by other threads, are not this batch's business
+int dl_wait(ald_batch *b)
+{
+    if(b->dl_shared) { HIPCHK(hipEventRecord(b->dl_done, b->dl_stream)); HIPCHK(hipEventSynchronize(b->dl_done)); }
+    else HIPCHK(hipStreamSynchronize(b->dl_stream));
+    return ALD_OK;
+}
+
 // The stage that ENDS a run, shared by ald_batch_finish and ald_batch_download: wait for the stream, status words, capacity retries one
-// class up, pool growth and a new run on ALD_ST_POOL_FULL, then the two counters.  Leaves b->status, b->used_words / used_index (clamped).
-// Everything comes back through async copies on the batch's OWN stream into pinned memory.  (A synchronous hipMemcpy runs on the
-// null stream, which waits for every blocking stream of the device -- i.e. for the kernel of the NEXT batch, already in flight in a
-// pipelined caller: the download of batch k took as long as the kernel of batch k+1, and its record copy ran between two kernels.)
+// class up, pool growth and a new run on ALD_ST_POOL_FULL, with the two counters of every pass.  Leaves b->status, b->used_words /
+// used_index (clamped).
+// Everything comes back through async copies into pinned memory on the batch's download stream (ald_internal.h: dl_stream), which shares
+// no hardware queue with a kernel.  Nothing orders that stream against b->stream on the device; the host does: no copy is issued before
+// the host has waited for b->stream (the head of every pass), and a retry pass or a new run goes on b->stream only after the host has
+// waited for the copies of the pass before it.  (A synchronous hipMemcpy runs on the null stream, which waits for every blocking stream
+// of the device -- i.e. for the kernel of the NEXT batch, already in flight in a pipelined caller: the download of batch k took as long
+// as the kernel of batch k+1, and its record copy ran between two kernels.)
 int end_run(ald_batch *b, EndStamps &T)
 {
     const int n = b->hb.n();
@@ -590,7 +643,11 @@ int end_run(ald_batch *b, EndStamps &T)
         if(pass == 0 && regrow == 0) T.P1 = std::chrono::steady_clock::now();
         float ms = 0; if(hipEventElapsedTime(&ms, b->ev0, b->ev1) == hipSuccess) b->kernel_ms += ms;
         b->passes++;
-        if(n > 0) { HIPCHK(hipMemcpyAsync(st, b->d_status.p, 4 * (size_t)n, hipMemcpyDeviceToHost, b->stream)); HIPCHK(hipStreamSynchronize(b->stream)); T.bytes += 4 * (int64_t)n; }
+        // the status words and the two pool counters in ONE round trip: the counters are only used once no retry pass is left, and a
+        // retry pass brings the pair again
+        if(n > 0) { HIPCHK(hipMemcpyAsync(st, b->d_status.p, 4 * (size_t)n, hipMemcpyDeviceToHost, b->dl_stream)); T.bytes += 4 * (int64_t)n; }
+        HIPCHK(hipMemcpyAsync(h_used, b->d_poolused.p, 16, hipMemcpyDeviceToHost, b->dl_stream)); T.bytes += 16;
+        { int rc = dl_wait(b); if(rc != ALD_OK) return rc; }
         if(pass == 0 && regrow == 0) T.P2 = std::chrono::steady_clock::now();
         // graphs whose working set overflowed their class are retried one class up (records carry the pass number)
         std::vector<int32_t> work[ALD_NUM_CLASSES]; bool any = false;
@@ -606,7 +663,7 @@ int end_run(ald_batch *b, EndStamps &T)
         int rc = launch_pass(b, work, pass + 1);
         if(rc != ALD_OK) return rc;
     }
-    HIPCHK(hipMemcpyAsync(h_used, b->d_poolused.p, 16, hipMemcpyDeviceToHost, b->stream)); HIPCHK(hipStreamSynchronize(b->stream)); used = h_used[0]; iused = h_used[1]; T.bytes += 16;
+    used = h_used[0]; iused = h_used[1];                   // of the last pass: every kernel of the run had ended when they were copied
     if(!pool_full) break;
     // Some graph found the record pool full.  Records behind the first refused one may be missing (the bump pointer moved, nothing was
     // written), so the stream of this run is unusable as a whole: the pool grows -- `used` counts every request made, a lower bound
@@ -627,16 +684,16 @@ int end_run(ald_batch *b, EndStamps &T)
     return ALD_OK;
 }
 
-// the per-graph counters: 16 bytes per graph, enqueued behind whatever the caller put on the batch's stream (which it then waits for)
+// the per-graph counters: 16 bytes per graph, enqueued on the download stream behind whatever the caller put there (which it then waits for)
 int enqueue_counters(ald_batch *b)
 {
     const int n = b->hb.n();
     if(n == 0) return ALD_OK;
     long long *h_gf = (long long*)((uint8_t*)b->pin_small.p + 64);
     int32_t *h_np = (int32_t*)(h_gf + n) + n, *h_ni = h_np + n;
-    HIPCHK(hipMemcpyAsync(h_np, b->d_npaths.p, 4 * (size_t)n, hipMemcpyDeviceToHost, b->stream));
-    HIPCHK(hipMemcpyAsync(h_ni, b->d_niters.p, 4 * (size_t)n, hipMemcpyDeviceToHost, b->stream));
-    HIPCHK(hipMemcpyAsync(h_gf, b->d_gfirst.p, 8 * (size_t)n, hipMemcpyDeviceToHost, b->stream));
+    HIPCHK(hipMemcpyAsync(h_np, b->d_npaths.p, 4 * (size_t)n, hipMemcpyDeviceToHost, b->dl_stream));
+    HIPCHK(hipMemcpyAsync(h_ni, b->d_niters.p, 4 * (size_t)n, hipMemcpyDeviceToHost, b->dl_stream));
+    HIPCHK(hipMemcpyAsync(h_gf, b->d_gfirst.p, 8 * (size_t)n, hipMemcpyDeviceToHost, b->dl_stream));
     return ALD_OK;
 }
 void take_counters(ald_batch *b)
@@ -660,7 +717,7 @@ int ald_batch_finish(ald_batch *b)
     EndStamps T;
     { int rc = end_run(b, T); if(rc != ALD_OK) return rc; }
     { int rc = enqueue_counters(b); if(rc != ALD_OK) return rc; }
-    HIPCHK(hipStreamSynchronize(b->stream));
+    { int rc = dl_wait(b); if(rc != ALD_OK) return rc; }       // returns with the download stream drained: the batch's next run, clear or upload cannot overtake a copy
     take_counters(b);
     // the row prefix of the (graph, path) order, exactly as HostResults::build forms it: only graphs that ended well have paths
     const long long *h_gf = (const long long*)((const uint8_t*)b->pin_small.p + 64);
@@ -715,14 +772,15 @@ int ald_batch_download(ald_batch *b)
     const unsigned long long used = b->used_words, iused = b->used_index;
     long long *h_gf = (long long*)((uint8_t*)b->pin_small.p + 64);
     b->res.clear();
-    // the records land in a pinned buffer (kept across runs) through an async copy on the batch stream: the copy engine moves them
-    // while another batch's kernel may be running, and the host thread only waits
+    // the records land in a pinned buffer (kept across runs) through an async copy on the download stream: the copy engine moves them
+    // while another batch's kernel may be running, and the host thread only waits.  (end_run, or the ald_batch_finish before this call,
+    // waited for the batch's own stream: the kernels that wrote the records are through.)
     if(b->pin_out.ensure(4 * (size_t)used + 64, true) || b->pin_index.ensure(8 * (size_t)iused + 64, true)) return set_err(ALD_ERR_NOMEM, "pinned result buffer");
     P3 = std::chrono::steady_clock::now();
     if(!ended) { int rc = enqueue_counters(b); if(rc != ALD_OK) return rc; }
-    if(iused) HIPCHK(hipMemcpyAsync(b->pin_index.p, b->d_index.p, 8 * iused, hipMemcpyDeviceToHost, b->stream));
-    if(used) HIPCHK(hipMemcpyAsync(b->pin_out.p, b->d_pool.p, 4 * used, hipMemcpyDeviceToHost, b->stream));
-    HIPCHK(hipStreamSynchronize(b->stream));
+    if(iused) HIPCHK(hipMemcpyAsync(b->pin_index.p, b->d_index.p, 8 * iused, hipMemcpyDeviceToHost, b->dl_stream));
+    if(used) HIPCHK(hipMemcpyAsync(b->pin_out.p, b->d_pool.p, 4 * used, hipMemcpyDeviceToHost, b->dl_stream));
+    { int rc = dl_wait(b); if(rc != ALD_OK) return rc; }
     const auto P3b = std::chrono::steady_clock::now();
     if(!ended) take_counters(b);
     b->res.ext_pool = (const uint32_t*)b->pin_out.p; b->res.ext_words = used;

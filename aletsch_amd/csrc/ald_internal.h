@@ -128,6 +128,16 @@ struct ald_batch {
     // of ANOTHER batch's kernel launch on the same queue delayed that kernel by 3-4 ms per step of a pipelined caller
     // (profiles/r04/zc_h2d_inclusive_step.txt).  Streams of a different priority have queues of their own.
     hipStream_t up_stream = nullptr;
+    // The RESULTS leave through a stream of a priority class no kernel runs in, for the same reason seen from the other side: four rotating
+    // batches own 28 normal-priority streams on 4 queues, so one batch's `stream` shares a queue with the side stream ANOTHER batch's class
+    // kernel runs on, and the first small copy issued on `stream` right after the caller launched that kernel -- the 16-byte pool counters:
+    // the runtime moves a copy that small with a blit kernel, i.e. through the queue -- waited for all of it (one download in four: 38 ms
+    // instead of 0.15, profiles/r15/).  Every D2H copy of end_run / ald_batch_finish / ald_batch_download goes to dl_stream after the host
+    // has waited for `stream`; `stream` and the side streams carry memsets, kernels and events only.
+    // ALD_DOWNLOAD_STREAM: 2 (default) ONE stream per device in the highest class, shared by the batches (dl_shared: a download then waits
+    // for dl_done, its own event, never for the stream); 1 a stream of the batch's own in the lowest class (measured: one batch object in
+    // four still waits 36 ms there); 0 or no second priority: `stream`.
+    hipStream_t dl_stream = nullptr; hipEvent_t dl_done = nullptr; bool dl_shared = false;
     // the size classes run concurrently on a few side streams.  Not one per class: a process only gets a handful of hardware queues
     // (4 by default) and streams beyond that share them in creation order, which can put the two heaviest classes behind each other
     hipStream_t cstream[ALD_SIDE_STREAMS_MAX] = {}; int n_cstream = ALD_SIDE_STREAMS;
