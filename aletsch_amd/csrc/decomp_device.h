@@ -141,6 +141,7 @@ struct HotCtx {
     int32_t  maybe_broken;                      // 0 => no vertex can be broken (a degree only reaches 0 in unlink_*; new vertices appear in extend)
     // state of the trivial-vertex sweep in flight (scan_trivial <-> sweep_trivial)
     double   sw_best_r, sw_hit_r; int32_t sw_best_v, sw_hit, sw_vend, sw_dom_base; uint32_t sw_need_lo, sw_need_hi;
+    int32_t  sw_ncand;                          // candidates the last scan saw, or -1 where it did not see them all (scan_trivial)
     int32_t  scr_i[SCR_I]; double scr_d[SCR_D];
 #ifdef ALD_PROF
     unsigned long long prof[32];
@@ -2191,7 +2192,8 @@ ALD_FN int scan_trivial(int start, int mode, int type, double jump_ratio)
     double best_r = HC.sw_best_r; int best_v = HC.sw_best_v;
     const int dom_base = HC.sw_dom_base;        // chunk whose dominate queries the driver has answered (scr_i[lane]), or -1
     int code = SC_NONE, hit = -1; double hit_r = 0;
-    double frr = DBL_MAX; int fvv = -1;          // this lane's best candidate over the chunks scanned (later vertex wins ties)
+    int ncand = 0;                               // candidates seen, all chunks together (wave-uniform: popcounts of the `cand` ballots)
+    double frr = DBL_MAX; int fvv = -1;         // this lane's best candidate over the chunks scanned (later vertex wins ties)
 #if ALD_KEEP_TRIV
     // The slab-resident classes keep (class, balance ratio) of every vertex in the wave's slab between the scans, as the smallest-edge sweep keeps its
     // evaluations: first the vertices marked since the last scan -- in dense lanes --, or all of them; then every chunk of the scan is one
@@ -2284,6 +2286,7 @@ ALD_FN int scan_trivial(int start, int mode, int type, double jump_ratio)
         uint64_t need = wballot(cls == -2);
         if(need) { if(lane == 0) { HC.sw_dom_base = base; HC.sw_need_lo = (uint32_t)need; HC.sw_need_hi = (uint32_t)(need >> 32); } code = SC_NEED; break; }
         bool cand = (cls == type);
+        ncand += (int)__builtin_popcountll(wballot(cand));
         if(cand) { if(kept) bad = kbad; else { bool ok; r = compute_balance_ratio(i, ok); if(!ok) bad = true; } }
         if(wballot(bad)) { code = SC_BAD; break; }
         uint64_t now = wballot(cand && r < now_thr);
@@ -2302,9 +2305,21 @@ ALD_FN int scan_trivial(int start, int mode, int type, double jump_ratio)
         wave_argmin(rr, vv);                                             // (all 64 lanes are here: the loop above leaves through wave-uniform breaks only)
         if(vv >= 0 && !(best_r < rr)) { best_r = rr; best_v = vv; }      // if(ratio < r) continue;
     }
-    if(lane == 0) { HC.sw_best_r = best_r; HC.sw_best_v = best_v; HC.sw_hit = hit; HC.sw_hit_r = hit_r; }
+    // the count stands for the whole graph only where the scan began at the first vertex and ran through every chunk to the end
+    if(lane == 0) { HC.sw_best_r = best_r; HC.sw_best_v = best_v; HC.sw_hit = hit; HC.sw_hit_r = hit_r; HC.sw_ncand = (start == 1 && code == SC_NONE) ? ncand : -1; }
     wsync();
     return code;
+}
+// test build of the emulation: a scan that maybe_triv == 0 skips must be one that finds no type-1 vertex
+ALD_INL void check_no_trivial_candidate()
+{
+#if defined(ALD_EMU) && defined(ALD_EMU_CHECK)
+    for(int v = 1; v < HC.nv; v++) {
+        const int d1 = H.vx[v].in_deg, d2 = H.vx[v].out_deg;
+        if(!(H.nz[v] & NZ_MEMBER) || d1 < 1 || d2 < 1 || (d1 >= 2 && d2 >= 2) || mixed_strand_vertex(v)) continue;
+        if(classify_trivial_vertex(v, true) == 1) { fprintf(stderr, "[check] graph %d: trivial-vertex scan skipped while vertex %d (degrees %d, %d) is a type-1 candidate\n", HC.g, v, d1, d2); abort(); }
+    }
+#endif
 }
 // The count of rule firings (HotCtx::n_iters, reported per graph) is kept in a register while a sweep runs and added once when it ends, and
 // the arguments of an op-trace event are only formed when a trace is being taken: trace() itself costs a read-modify-write of the counter
@@ -2328,10 +2343,10 @@ ALD_INL bool sweep_trivial_body(int mode, int type, double jump_ratio, int &fire
     // skipped.  (Stranded graphs also gain candidates when a removal un-mixes a vertex: they always scan.)
     const int hsd_q = HC.hs_dirty, strand_q = HC.any_strand, triv_q = HC.maybe_triv, nv_q = HC.nv;      // one round of LDS reads for the tests below
     const bool skippable = (mode == 1 && type == 1 && !uni(strand_q));
-    if(skippable && !uni(hsd_q) && !uni(triv_q)) return false;                // (a pending flag refresh raises maybe_triv itself: not skipped then)
+    if(skippable && !uni(hsd_q) && !uni(triv_q)) { check_no_trivial_candidate(); return false; }     // (a pending flag refresh raises maybe_triv itself: not skipped then)
     if(lane == 0) { if(uni(hsd_q)) hs_refresh_flags(); HC.sw_vend = nv_q; HC.sw_best_r = DBL_MAX; HC.sw_best_v = -1; HC.sw_dom_base = -1; }
     wsync();
-    if(skippable && !uni(HC.maybe_triv)) return false;
+    if(skippable && !uni(HC.maybe_triv)) { check_no_trivial_candidate(); return false; }
     bool flag = false;
     int start = 1;
     // ONE place decomposes -- the vertex a scan hits (the sweep then goes on behind it) or, when the sweep ends without a hit, its best
@@ -2359,6 +2374,13 @@ ALD_INL bool sweep_trivial_body(int mode, int type, double jump_ratio, int &fire
             if(mode == 0) return false;
             if(uni(HC.sw_best_v) < 0) { if(skippable) { if(lane == 0) HC.maybe_triv = 0; wsync(); } return false; }
             target = uni(HC.sw_best_v); last = true;
+#ifndef ALD_NO_TRIV_CLEAR
+            // The scan saw every vertex and this one candidate only, and no hit came before it (`flag`): once it is decomposed no type-1 vertex is
+            // left, unless the star makes one -- by a degree that drops to <= 1, new phasing flags or a new vertex, each of which raises
+            // maybe_triv again.  Cleared here, the scan that would end this run of trivial decompositions by finding nothing is not made:
+            // the next turn of the cascade leaves sweep_trivial at its first test.  (-DALD_NO_TRIV_CLEAR: the flag stays up until that scan.)
+            if(skippable && uni(HC.sw_ncand) == 1) { if(lane == 0) HC.maybe_triv = 0; wsync(); }
+#endif
         }
         fired++;
         if(tr && lane == 0) { if(last) trace_emit(OP_TRIVIAL_BEST, vlog(target), type, HC.sw_best_r); else trace_emit(mode == 1 ? OP_TRIVIAL_NOW : OP_TRIVIAL_FAST, vlog(target), mode == 1 ? type : 0, HC.sw_hit_r); }

@@ -16,7 +16,7 @@
 // target through the wave -- no atomic decides an order, so the result is the host's counting sort whatever the scheduling.
 // ONE form for every graph (any size: add takes graphs far beyond the largest class): c[] IS the graph's in_offset slots in global memory.
 // No LDS, no scratch buffer, and at most ALD_EXPAND_VGPRS registers per lane -- on purpose.  A pipelined caller uploads batch k + 1 while
-// the persistent class kernels of batch k hold the CUs: the class-1 kernel (the bench shape) keeps 20 workgroups of 8 176 B on a CU --
+// the persistent class kernels of batch k hold the CUs: the class-1 kernel (the bench shape) keeps 20 workgroups of 8 184 B on a CU --
 // 163 520 of its 163 840 B of LDS -- and 5 x 96 of a SIMD's 512 VGPRs.  An expand wave that asks for 4 KB of LDS, as the first form of
 // this kernel did, gets on a CU only when class workgroups retire (upload 33 ms instead of 24 in bench.py's loop); one that asks for no
 // LDS and 32 VGPRs fits into what that kernel leaves free.
