@@ -5,7 +5,7 @@ derived on the device (aletsch_amd/csrc/input_expand.h) instead of copied to it.
    and compares every section of the device buffer with the host's staging, byte for byte.
 2. The seeded mix of tests/class_cases.py, the hub batch of tests/shapes.py and a raw batch give the same answer with the bit set and
    with it clear: status, path and iteration counts, every record the result index names (all of its words) and the index's shape, op
-   traces, the features_all tables bit for bit, ald_batch_algorithmic_bytes.  WHERE a record lies in the pool is decided by which
+   traces, every field of the features_all tables bit for bit, ald_batch_algorithmic_bytes.  WHERE a record lies in the pool is decided by which
    wave bumps the pool pointer first and differs between two runs of the same build, so the records are compared through the index:
    record (g, p) of one run against record (g, p) of the other, word for word, and the totals of both.
 3. One batch object reused: compact upload, run, download, clear, other graphs, upload, run == a fresh batch.
@@ -80,7 +80,10 @@ def _answer(stage, params, n_trace=0, raw_features_on_device=False):
         ans = dict(status=st.copy(), npaths=npth.copy(), iters=nit.copy(), iterations=b.iterations().copy(), recs=recs, words=words, entries=entries,
                    traces=[b.trace(g) for g in range(0, min(b.n, n_trace), CC.TRACE_STRIDE)], bytes=b.algorithmic_bytes())
         f = b.features_all(raw_on_device=raw_features_on_device)
-        ans["feat"] = {k: f[k].tobytes() for k in ("rows", "complete", "graph_rc", "row_begin")}
+        ans["feat"] = {k: f[k].tobytes() for k in ("complete", "graph_rc", "row_begin")}
+        # every FIELD of every row bit for bit.  Not the 4-byte holes between the fields: the kernel stores end_cnt with a dwordx2 whose upper
+        # half is the old content of a register, so two runs of the SAME build differed there (seen with the parent commit's library too)
+        ans["feat"]["rows"] = {name: np.ascontiguousarray(f["rows"][name]).tobytes() for name in f["rows"].dtype.names}
         ans["feat_one"] = [_features_of(b, g) for g in range(0, b.n, max(1, b.n // 7))]      # the per-graph host routine reads the in-CSR, which a compact batch builds on demand
     return ans
 
