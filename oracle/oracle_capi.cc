@@ -22,6 +22,7 @@ struct GraphResult {
     std::vector<ora::TraceEvent> trace;
     ora::Stats st;
     ora::Census census;
+    ora::SweepCensus sweeps;
     int feature_assert = 0;
 };
 
@@ -87,7 +88,7 @@ void run_one(const Packed &P, const Offsets &o, int g, const ora::Params &cfg, b
     try {
         ora::Scallop sc(gr, hs, cfg);
         if(want_trace) sc.trace = &out.trace;
-        sc.census = &out.census;
+        sc.census = &out.census; sc.sweeps = &out.sweeps;
         sc.assemble();
         out.paths = sc.paths; out.trsts = sc.trsts; out.st = sc.st; out.iterations = sc.st.iterations; out.feature_assert = sc.feature_assert;
         if(sc.st.cut_short) out.status = ALD_ST_SKIPPED_LARGE;        // the loop left through `num_vertices() > max_num_exons` (scallop.cc:49), at the start or after growing
@@ -244,6 +245,18 @@ int ora_result_census(const ora_result *R, int32_t graph, int32_t *n_rows, int32
     if(!rows7) return 0;
     int i = 0;
     for(auto &kv : c) { if(i >= cap) break; for(int k = 0; k < 6; k++) rows7[7 * i + k] = kv.first[k]; rows7[7 * i + 6] = kv.second; i++; }
+    return 0;
+}
+
+/* census of one graph's sweeps (scallop_oracle.hpp: SweepCensus): *n_rows rows of 14 ints = the thirteen key fields + the number of events; rows14 == null
+ * asks for the number of rows only */
+int ora_result_sweep_census(const ora_result *R, int32_t graph, int32_t *n_rows, int32_t *rows14, int32_t cap)
+{
+    const ora::SweepCensus &c = R->gr[graph].sweeps;
+    *n_rows = (int32_t)c.size();
+    if(!rows14) return 0;
+    int i = 0;
+    for(auto &kv : c) { if(i >= cap) break; for(int k = 0; k < 13; k++) rows14[14 * i + k] = kv.first[k]; rows14[14 * i + 13] = kv.second; i++; }
     return 0;
 }
 

@@ -41,6 +41,7 @@
 #include <climits>
 #include <cstdint>
 #include <cstdio>
+#include <cstring>
 #include <string>
 
 namespace ora {
@@ -767,6 +768,23 @@ struct Stats { int max_live_edges = 0, max_vertices = 0, total_edge_ids = 0, ite
 //   trivial decompositions: {0, direction (0: one in-edge, the fan goes out; 1: one out-edge, the fan comes in), fan size, 0, 0, 0}
 //   router builds:          {1, in-degree, out-degree, graph has phasing lists, every counted edge has ONE sample, some edge has count 0}
 typedef std::map<std::array<int, 6>, int> Census;
+// How every vertex-selection sweep of the rule cascade ended, for the tests that must know which ties, thresholds and lane positions a batch
+// puts in front of the kernel's wave-parallel selections (tests/sweep_cases.py).  A map of its own: the readers of Census tell its two kinds
+// apart by key[0] == 0.  One event per sweep that fired; key =
+//   [0] rule: 1 / 2 resolve_trivial_vertex of that type, 3 resolve_trivial_vertex_fast, 4 resolve_smallest_edges, 5 / 6 resolve_unsplittable_vertex
+//       (UNSPLITTABLE_SINGLE / SPLITTABLE_PURE)
+//   [1] how it ended: 1 now (a candidate under the fixed threshold fired), 2 stop (`ratio < jump_ratio` broke the loop), 3 best
+//   [2] candidates, [3] candidates whose ratio equals the winner's (the winner: the root, or the first `now` vertex)
+//   [4], [5] the winner as (vertex / 64, vertex % 64); [6], [7] the first tied loser likewise, or -1
+//   [8] bit 0: the winner's ratio equals the fixed threshold (1.02 / 0.01), bit 1: it equals the rule's parameter, bit 2: a candidate that did not
+//       fire `now` has exactly the fixed threshold, bit 3 (fast sweep): a candidate was refused with exactly jump_ratio, bit 4 (fast sweep): one was
+//       taken with a ratio of 1.02 or more
+//   [9] two candidates with different ratios share the upper 32 bits of the double
+//   [10] where the first candidate of bit 2 stands to the first `now` vertex: 1 / 2 in front of it in the same / another chunk of 64, 3 / 4 behind; 0: no such pair
+//   [11] the same for the first stop candidate (1.02 <= r < jump_ratio) and the first `now` vertex -- the one the loop never reached included
+//   [12] smallest-edge sweep, at the winner: bit 0 two edges of the chosen side share the minimal weight, bit 1 r1 == r2 between the two sides
+typedef std::map<std::array<int, 13>, int> SweepCensus;
+struct SweepCand { int v; double r; bool now; };
 
 // ---------------------------------------------------------------------------------------------
 // scallop (scallop/scallop.cc)
@@ -777,6 +795,7 @@ struct Scallop {
     std::vector<int> v2v; std::set<int> nonzeroset;
     std::vector<Path> paths; std::vector<Transcript> trsts;
     std::vector<TraceEvent> *trace = nullptr; Stats st; Census *census = nullptr;        // where the caller wants the census (it outlives a run that ends on an assert)
+    SweepCensus *sweeps = nullptr;              // likewise, the census of the sweeps
     Graph gr_ori;
     int feature_assert = 0;                     // line of the first assert update_trst_features would have hit (0: none); the paths stand either way
 
@@ -837,13 +856,36 @@ struct Scallop {
         return true;
     }
 
-    bool resolve_single_trivial_vertex(int i, double jump_ratio) {   // scallop.cc:1236-1254
+    static int sweep_relation(int x, int now) { return x < 0 || now < 0 ? 0 : (x < now ? 1 : 3) + (x / 64 != now / 64 ? 1 : 0); }
+    void census_sweep(int rule, int end, int winner, double fixed_thr, double param, const std::vector<SweepCand> &c, int stop_v = -1, int unseen_now = -1, int extra = 0, int inner = 0) {
+        if(!sweeps || winner < 0) return;
+        double wr = 0;
+        for(auto &x : c) if(x.v == winner) wr = x.r;
+        int ntied = 0, loser = -1, first_now = -1, exact = -1, mask = extra;
+        std::map<uint32_t, std::set<uint32_t>> words;
+        for(auto &x : c) {
+            if(x.r == wr) { ntied++; if(x.v != winner && loser < 0) loser = x.v; }
+            if(x.now && first_now < 0) first_now = x.v;
+            if(!x.now && x.r == fixed_thr && exact < 0) exact = x.v;
+            uint64_t u; memcpy(&u, &x.r, 8); words[(uint32_t)(u >> 32)].insert((uint32_t)u);
+        }
+        if(wr == fixed_thr) mask |= 1;
+        if(wr == param) mask |= 2;
+        if(exact >= 0) mask |= 4;
+        int shared = 0; for(auto &kv : words) if(kv.second.size() >= 2) shared = 1;
+        if(first_now < 0) first_now = unseen_now;
+        (*sweeps)[{rule, end, (int)c.size(), ntied, winner / 64, winner % 64, loser < 0 ? -1 : loser / 64, loser < 0 ? -1 : loser % 64, mask, shared,
+                   sweep_relation(exact, first_now), sweep_relation(stop_v, first_now), inner}]++;
+    }
+
+    bool resolve_single_trivial_vertex(int i, double jump_ratio, std::vector<SweepCand> *seen = nullptr) {   // scallop.cc:1236-1254
         if(gr.in_degree(i) <= 0) return false;
         if(gr.out_degree(i) <= 0) return false;
         if(gr.in_degree(i) >= 2 && gr.out_degree(i) >= 2) return false;
         if(gr.mixed_strand_vertex(i)) return false;
         if(classify_trivial_vertex(i, false) != 1) return false;
         double r = compute_balance_ratio(i);
+        if(seen) seen->push_back({i, r, !(r >= jump_ratio)});
         if(r >= jump_ratio) return false;
         ev(OP_TRIVIAL_FAST, i, 0, r);
         decompose_trivial_vertex(i);
@@ -853,19 +895,28 @@ struct Scallop {
     bool resolve_trivial_vertex_fast(double jump_ratio) {            // scallop.cc:1256-1270
         bool flag = false;
         std::vector<int> vv(nonzeroset.begin(), nonzeroset.end());
-        for(int i : vv) if(resolve_single_trivial_vertex(i, jump_ratio)) flag = true;
+        std::vector<SweepCand> seen;
+        for(int i : vv) if(resolve_single_trivial_vertex(i, jump_ratio, sweeps ? &seen : nullptr)) flag = true;
+        if(flag && sweeps) {
+            int first = -1, extra = 0;
+            for(auto &x : seen) { if(x.now && first < 0) first = x.v; if(!x.now && x.r == jump_ratio) extra |= 8; if(x.now && !(x.r < 1.02)) extra |= 16; }
+            census_sweep(3, 1, first, 1.02, jump_ratio, seen, -1, -1, extra);
+        }
         return flag;
     }
     bool resolve_trivial_vertex(int type, bool fast, double jump_ratio) {   // scallop.cc:1180-1234
         int root = -1; double ratio = DBL_MAX; bool flag = false;
         std::vector<int> vv(nonzeroset.begin(), nonzeroset.end());
-        for(int i : vv) {
+        std::vector<SweepCand> seen; int first_now = -1, stop_v = -1, unseen_now = -1;
+        for(size_t k = 0; k < vv.size(); k++) {
+            int i = vv[k];
             if(gr.in_degree(i) <= 0) continue;
             if(gr.out_degree(i) <= 0) continue;
             if(gr.mixed_strand_vertex(i)) continue;
             if(gr.in_degree(i) >= 2 && gr.out_degree(i) >= 2) continue;
             if(classify_trivial_vertex(i, fast) != type) continue;
             double r = compute_balance_ratio(i);
+            if(sweeps) { seen.push_back({i, r, r < 1.02}); if(r < 1.02 && first_now < 0) first_now = i; }
             if(r < 1.02) {
                 ev(OP_TRIVIAL_NOW, i, type, r);
                 decompose_trivial_vertex(i);
@@ -874,10 +925,20 @@ struct Scallop {
             }
             if(ratio < r) continue;
             root = i; ratio = r;
-            if(ratio < jump_ratio) break;
+            if(ratio < jump_ratio) {
+                stop_v = i;
+                if(sweeps && first_now < 0) for(size_t q = k + 1; q < vv.size() && unseen_now < 0; q++) {      // (census only: the `now` vertex the loop does not reach)
+                    int j = vv[q];
+                    if(gr.in_degree(j) <= 0 || gr.out_degree(j) <= 0 || gr.mixed_strand_vertex(j) || (gr.in_degree(j) >= 2 && gr.out_degree(j) >= 2)) continue;
+                    try { if(classify_trivial_vertex(j, fast) == type && compute_balance_ratio(j) < 1.02) unseen_now = j; }
+                    catch(const AssertFail &) {}                     // (an assert the reference's loop does not reach must not end the run)
+                }
+                break;
+            }
         }
-        if(flag) return true;
+        if(flag) { census_sweep(type, 1, first_now, 1.02, jump_ratio, seen, stop_v); return true; }
         if(root == -1) return false;
+        census_sweep(type, stop_v >= 0 ? 2 : 3, root, 1.02, jump_ratio, seen, stop_v, unseen_now);
         ev(OP_TRIVIAL_BEST, root, type, ratio);
         decompose_trivial_vertex(root);
         ORA_ASSERT(INV_DEGREE, gr.degree(root) == 0);
@@ -904,9 +965,16 @@ struct Scallop {
         if(r1 < r2) { ratio = r1; return e1; }
         ratio = r2; return e2;
     }
+    int census_inner_ties(int x, int e) {                  // SweepCensus key[12] for vertex x whose smallest edge is e
+        double r1, r2; compute_smallest_in_edge(x, r1); compute_smallest_out_edge(x, r2);
+        int same = 0;
+        for(int id : (gr.et[e] == x ? gr.in_edges(x) : gr.out_edges(x))) if(gr.ewrt[id] == gr.ewrt[e]) same++;
+        return (same >= 2 ? 1 : 0) | (r1 == r2 ? 2 : 0);
+    }
     bool resolve_smallest_edges(double max_ratio) {        // scallop.cc:844-945
         int se = -1, root = -1; double ratio = max_ratio; bool flag = false;
         std::vector<int> vv(nonzeroset.begin(), nonzeroset.end());
+        std::vector<SweepCand> seen; int first_now = -1;
         for(int i : vv) {
             if(gr.in_degree(i) <= 1) continue;
             if(gr.out_degree(i) <= 1) continue;
@@ -923,6 +991,7 @@ struct Scallop {
             int z = gr.einf[e].strand;
             if(s == i && z >= 1 && vs[0] + vs[z + 0] <= 1) continue;
             if(t == i && z >= 1 && vs[3] + vs[z + 3] <= 1) continue;
+            if(sweeps) { seen.push_back({i, r, r < 0.01}); if(r < 0.01 && first_now < 0) first_now = i; }
             if(r < 0.01) {
                 ev(OP_SMALL_NOW, e, i, r);
                 remove_edge(e); hs.remove(e);
@@ -931,8 +1000,9 @@ struct Scallop {
             if(ratio < r) continue;
             ratio = r; se = e; root = i;
         }
-        if(flag) return true;
+        if(flag) { census_sweep(4, 1, first_now, 0.01, max_ratio, seen); return true; }
         if(se == -1) return false;
+        if(sweeps) census_sweep(4, 3, root, 0.01, max_ratio, seen, -1, -1, 0, census_inner_ties(root, se));      // (no edge has gone: the graph is the one the loop saw)
         ev(OP_SMALLEST, se, root, ratio);
         remove_edge(se); hs.remove(se);
         return true;
@@ -940,6 +1010,7 @@ struct Scallop {
     bool resolve_unsplittable_vertex(int type, int degree, double max_ratio) {   // scallop.cc:1004-1060
         int root = -1; MPID pe2w; double ratio = max_ratio; bool flag = false;
         std::vector<int> vv(nonzeroset.begin(), nonzeroset.end());
+        std::vector<SweepCand> seen; int first_now = -1; const int rule = type == UNSPLITTABLE_SINGLE ? 5 : 6;
         for(int i : vv) {
             if(gr.in_degree(i) <= 1) continue;
             if(gr.out_degree(i) <= 1) continue;
@@ -949,6 +1020,7 @@ struct Scallop {
             if(rt.type != type) continue;
             if(rt.degree > degree) continue;
             census_router(i); rt.build(); st.router_builds++;
+            if(sweeps) { seen.push_back({i, rt.ratio, rt.ratio < 0.01}); if(rt.ratio < 0.01 && first_now < 0) first_now = i; }
             if(rt.ratio < 0.01) {
                 ev(OP_UNSPLIT_NOW, i, type, rt.ratio);
                 decompose_vertex_extend(i, rt.pe2w);
@@ -957,8 +1029,9 @@ struct Scallop {
             if(rt.ratio > ratio) continue;
             root = i; ratio = rt.ratio; pe2w = rt.pe2w;
         }
-        if(flag) return true;
+        if(flag) { census_sweep(rule, 1, first_now, 0.01, max_ratio, seen); return true; }
         if(root == -1) return false;
+        census_sweep(rule, 3, root, 0.01, max_ratio, seen);
         ev(OP_UNSPLIT_BEST, root, type, ratio);
         decompose_vertex_extend(root, pe2w);
         return true;
