@@ -29,6 +29,7 @@
 #ifdef ALD_EMU
 #include <cstdio>
 #include <cstdlib>
+namespace ald { inline int32_t *emu_fail_line = nullptr; }      // emulation only: [graph] -> the source line of the fail() that set its status, 0: none
 #endif
 
 #ifndef ALD_CLASS_ID
@@ -228,6 +229,7 @@ ALD_INL void fail_(int st, int line)
 {
 #ifdef ALD_EMU
     if(HC.status == 0 && getenv("ALD_EMU_VERBOSE")) fprintf(stderr, "[emu] graph %d: status %d raised at decomp_device.h:%d\n", HC.g, st, line);
+    if(HC.status == 0 && ald::emu_fail_line) ald::emu_fail_line[HC.g] = line;      // the first exit of this run of the graph (tests/kernel_emu/emu_capi.cc: emu_result_fail_lines)
 #endif
     if(HC.status == 0) HC.status = st;
 }
@@ -978,7 +980,7 @@ template<bool A, bool SMALL> ALD_INL void decompose_trivial_star(int x)
     double vwt = C.vx[x].vw; const int lt = uni(C.vx[x].lpos), rt = uni(C.vx[x].rpos), ov = uni(C.vx[x].v2v);
     bool consumed = false;
     for(int q = 0; q < n; q++) {
-        if(consumed) { C.vx[x].vw = vwt; fail(ALD_ST_INVARIANT + ALD_INV_OTHER); return; }     // the general form would be handed a dead edge here
+        if(consumed) { C.vx[x].vw = vwt; fail(ALD_ST_INVARIANT + ALD_INV_DEGREE); return; }     // c is gone and fan edges are left: merge_adjacent_edges returns -1 for each (scallop.cc:2397), then assert(gr.degree(root) == 0) (scallop.cc:2139)
         const int j = ord[q], f = fe[j]; const double ww = fw[j];
         const double wcur = H.ed[c].w;                                   // what is left of c
         const bool sc = uni(!(fabs(wcur - ww) <= kSMIN));                        // split_edge(c, ww) cuts a piece off (scallop.cc:2433-2484)
@@ -995,7 +997,10 @@ template<bool A, bool SMALL> ALD_INL void decompose_trivial_star(int x)
         const uint32_t nsf = uni(C.ed[f].sp_len); const int idf = uni(C.ed[f].s0id); const double abf = C.ed[f].s0abd;
         const uint64_t mk0 = C.ed[f].mask[0] | C.ed[c].mask[0];
         PROF_ADD(PF_T_MERGE_LOAD);
-        if(!(cntc > 0 && cntf > 0)) { C.vx[x].vw = vwt; fail(ALD_ST_INVARIANT + ALD_INV_COUNT); return; }
+        if(!(cntc > 0 && cntf > 0)) {      // (an infinite pair weight up to here would have ended the reference in merge_adjacent_equal_edges: fabs(inf - inf) is a NaN, scallop.cc:2242-2378)
+            bool inf_first = false; for(int qq = 0; qq <= q; qq++) if(!(fw[ord[qq]] <= DBL_MAX)) inf_first = true;
+            C.vx[x].vw = vwt; fail(ALD_ST_INVARIANT + (inf_first ? ALD_INV_MERGE_EQUAL : ALD_INV_COUNT)); return;
+        }
         if(nsc == 1 && nsf == 1) {      // one supporting sample on both sides: intersect_samples' inline case, c's half already in registers
             if(idf == idc) { const double xa = A ? abc : abf, ya = A ? abf : abc; const double mn = (ya < xa) ? ya : xa; C.ed[f].sp_off = 0; C.ed[f].ecount = 1; C.ed[f].eabd = 0.0 + mn; C.ed[f].s0abd = mn; }
             else { C.ed[f].sp_off = 0; C.ed[f].sp_len = 0; C.ed[f].ecount = 0; C.ed[f].eabd = 0; C.ed[f].s0id = 0; C.ed[f].s0abd = 0; }
@@ -1069,7 +1074,7 @@ template<bool A, bool SMALL> ALD_INL void decompose_trivial_star(int x)
         { const int dg = A ? (int)uni(H.vx[far].out_deg) : (int)uni(H.vx[far].in_deg); if(A) H.vx[far].out_deg = (IDX)(dg + n); else H.vx[far].in_deg = (IDX)(dg + n); ev_degree(far, dg, dg + n, A); }
     }
     if(n >= 2) hs_remove(c);
-    if(ALD_UNLIKELY(!consumed)) { fail(ALD_ST_INVARIANT + ALD_INV_DEGREE); return; }      // c kept a remainder: the reference asserts on the degree of x
+    if(ALD_UNLIKELY(!consumed)) { fail(ALD_ST_INVARIANT + (!(mdc <= DBL_MAX) ? ALD_INV_MERGE_EQUAL : ALD_INV_DEGREE)); return; }      // (an infinite pair weight: the reference's merge-equal assert) c kept a remainder: the reference asserts on the degree of x
     // remove_edge(c); x is left without edges
     if(A) unlink_out(far, c); else unlink_in(far, c);
     H.ed[c].lk.es = NIL; H.hflag[c] = 0;
@@ -1275,7 +1280,7 @@ template<bool A> ALD_INL void star_wave_body(int x)
         const uint32_t nsf = pf_ns; const int idf = pf_id; const double abf = pf_abd;
         {   // what the sequential form checks when it reaches merge q, in its order: a consumed c, the id counter, the two counts
             int code = 0;
-            if(dead) code = ALD_ST_INVARIANT + ALD_INV_OTHER;
+            if(dead) code = ALD_ST_INVARIANT + ALD_INV_DEGREE;     // (c is gone, fan edges are left: scallop.cc:2397, then the assert of scallop.cc:2139)
             else if(nid - (sc ? 1 : 0) >= EID_LIMIT) code = ALD_ST_CAPACITY;
             else if(!(cntc > 0 && cntf > 0)) code = ALD_ST_INVARIANT + ALD_INV_COUNT;
             inv[q] = code; if(ALD_UNLIKELY(code)) broken = true;
@@ -1302,7 +1307,11 @@ template<bool A> ALD_INL void star_wave_body(int x)
     const bool any_multi = wballot(multi) != 0;
     if(ALD_UNLIKELY(wballot(broken) != 0)) {                                    // the failure the sequence meets first: the smallest q that has one
         wsync();
-        if(lane == 0) for(int q = 0; q < n; q++) if(inv[q]) { fail(inv[q]); break; }
+        if(lane == 0) for(int q = 0; q < n; q++) if(inv[q]) {
+            int code = inv[q];
+            if(code == ALD_ST_INVARIANT + ALD_INV_COUNT) for(int qq = 0; qq <= q; qq++) if(!(fw[ord[qq]] <= DBL_MAX)) code = ALD_ST_INVARIANT + ALD_INV_MERGE_EQUAL;     // (an infinite pair weight in front of it: fabs(inf - inf) is a NaN in merge_adjacent_equal_edges)
+            fail(code); break;
+        }
         wsync();
         return;
     }
@@ -1312,7 +1321,7 @@ template<bool A> ALD_INL void star_wave_body(int x)
     if(lane == 0 && consumed) { if(A) unlink_out(far, c); else unlink_in(far, c); }
     wsync();
     PROF_ADD(PF_T_MERGE_MASK);
-    if(ALD_UNLIKELY(!consumed)) { if(lane == 0) fail(ALD_ST_INVARIANT + ALD_INV_DEGREE); wsync(); return; }     // c kept a remainder: the reference asserts on the degree of x
+    if(ALD_UNLIKELY(!consumed)) { if(lane == 0) fail(ALD_ST_INVARIANT + (!(dctx[0] <= DBL_MAX) ? ALD_INV_MERGE_EQUAL : ALD_INV_DEGREE)); wsync(); return; }     // c kept a remainder: the reference asserts on the degree of x -- or, with an infinite pair weight, in merge_adjacent_equal_edges
     // ---- phase 6 (lane q): place of merged edge q in far's list = behind the last old entry whose key does not exceed its own
     // (old entries carry older ids), and among the new ones by (key, creation order).  Read-only walk; the links are written in 6c.
     int32_t *pred = inv, *succ = (int32_t*)sq, *srt = (int32_t*)sq + STAR_MAX;
@@ -1474,7 +1483,7 @@ template<bool A> ALD_INL void star_reg(int x)
     for(int q = 0; q < n; q++) {
         const int src0 = ffs64(wballot(act && inv == q)), src = src0 < 0 ? 0 : src0;
         const double ww = wread(fw, src);
-        if(q > 0) { if(!sc && failq < 0) { failq = q; failcode = ALD_ST_INVARIANT + ALD_INV_OTHER; } wcur = rem; nid += 1; }      // (the general form would be handed a dead edge here)
+        if(q > 0) { if(!sc && failq < 0) { failq = q; failcode = ALD_ST_INVARIANT + ALD_INV_DEGREE; } wcur = rem; nid += 1; }      // (c is gone, fan edges are left: scallop.cc:2397, then the assert of scallop.cc:2139)
         sc = uni(!(fabs(wcur - ww) <= kSMIN));                                // split_edge(c, ww) cuts a piece off (scallop.cc:2433-2484)
         rem = wcur; if(sc) { nid += 1; rem = wcur - ww; if(rem <= mw) rem = mw; }
         if(failq < 0 && nid - (sc ? 1 : 0) >= EID_LIMIT) { failq = q; failcode = ALD_ST_CAPACITY; }
@@ -1499,10 +1508,15 @@ template<bool A> ALD_INL void star_reg(int x)
         else { uint64_t m = wballot(act && !(pf_cnt > 0)); while(m) { const int l = ffs64(m); m &= m - 1; const int ql = wread(inv, l); if(cq < 0 || ql < cq) cq = ql; } }
         int code = 0;
         if(failq >= 0 && (cq < 0 || failq <= cq)) code = failcode; else if(cq >= 0) code = ALD_ST_INVARIANT + ALD_INV_COUNT;
-        if(ALD_UNLIKELY(code != 0)) { if(lane == 0) { C.vx[x].vw = vwt; fail(code); } wsync(); return; }
+        if(ALD_UNLIKELY(code != 0)) {
+            if(code == ALD_ST_INVARIANT + ALD_INV_COUNT && !(rem <= DBL_MAX)) {      // (what is left of c is inf or a NaN once a pair weight is infinite)      // an infinite pair weight in front of the count: the reference's merge-equal assert
+                for(int q = 0; q <= cq; q++) { const int s0 = ffs64(wballot(act && inv == q)); const double pw = wread(fw, s0 < 0 ? 0 : s0); if(!(pw <= DBL_MAX)) code = ALD_ST_INVARIANT + ALD_INV_MERGE_EQUAL; }
+            }
+            if(lane == 0) { C.vx[x].vw = vwt; fail(code); } wsync(); return;
+        }
     }
     if(lane == 0) C.vx[x].vw = vwt;
-    if(ALD_UNLIKELY(!consumed)) { if(lane == 0) fail(ALD_ST_INVARIANT + ALD_INV_DEGREE); wsync(); return; }     // c kept a remainder: the reference asserts on the degree of x
+    if(ALD_UNLIKELY(!consumed)) { if(lane == 0) fail(ALD_ST_INVARIANT + (!(rem <= DBL_MAX) ? ALD_INV_MERGE_EQUAL : ALD_INV_DEGREE)); wsync(); return; }     // c kept a remainder: the reference asserts on the degree of x
     // two fan edges to one vertex: their relinks share a list -> sequential, in merge order, at the end
     bool dup = false;
     for(int k = 0; k < n; k++) { const int othk = wread(oth, k); if(act && lane != k && othk == oth) dup = true; }
@@ -2288,7 +2302,14 @@ ALD_FN int scan_trivial(int start, int mode, int type, double jump_ratio)
         bool cand = (cls == type);
         ncand += (int)__builtin_popcountll(wballot(cand));
         if(cand) { if(kept) bad = kbad; else { bool ok; r = compute_balance_ratio(i, ok); if(!ok) bad = true; } }
-        if(wballot(bad)) { code = SC_BAD; break; }
+        {   // the reference meets the vertices in order (scallop.cc:1180-1234): a weight sum below SMIN asserts only if no vertex in front of it, in
+            // this chunk, fires `now` or stops the sweep -- that one is taken first, and the scan that follows meets the assert in its turn
+            if(wballot(bad)) {
+                const uint64_t badm = wballot(bad);
+                const uint64_t ev = wballot(cand && !bad && (r < now_thr || (mode == 1 && r < jump_ratio)));
+                if(!(ev & ((1ull << ffs64(badm)) - 1))) { code = SC_BAD; break; }
+            }
+        }
         uint64_t now = wballot(cand && r < now_thr);
         // scallop.cc:1222 `if(ratio < jump_ratio) break;`: the first candidate with 1.02 <= r < jump_ratio becomes the root and ends the sweep
         uint64_t stp = (mode == 1) ? wballot(cand && !(r < now_thr) && r < jump_ratio) : 0ull;
@@ -2517,8 +2538,9 @@ ALD_INL bool sweep_smallest_body(double max_ratio, int &fired, const bool tr)
                 if(c < c0 || c * ALD_WAVE >= vend || hit >= 0 || badw) continue;          // (wave-uniform)
                 const int i = c * ALD_WAVE + lane;
                 const int e = (i >= start && i < vend) ? ce[c] : -1;
-                if(wballot(e == -3)) { badw = true; continue; }
+                const uint64_t badm = wballot(e == -3);
                 const uint64_t now = wballot(e >= 0 && cr[c] < 0.01);
+                if(ALD_UNLIKELY(badm != 0) && (!now || ffs64(badm) < ffs64(now))) { badw = true; continue; }     // (in the reference's order, scallop.cc:844-945: a `now` vertex in front of the assert fires first)
                 if(now) { const int l = ffs64(now); hit = c * ALD_WAVE + l; hit_e = wread(e, l); hit_r = wread(cr[c], l); }
             }
             if(badw) { if(lane == 0) fail(ALD_ST_INVARIANT + ALD_INV_WEIGHT); wsync(); return true; }

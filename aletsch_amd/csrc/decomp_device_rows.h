@@ -31,6 +31,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <vector>
+namespace ald { inline int32_t *emu_fail_line = nullptr; }      // emulation only: [graph] -> the source line of the fail() that set its status, 0: none
 #endif
 
 #ifndef ALD_CLASS_ID
@@ -213,7 +214,8 @@ enum { PF_LOAD = 0, PF_BROKEN, PF_TRIV_EVAL, PF_TRIV_MUT, PF_SMALL_EVAL, PF_SMAL
 ALD_INL void fail_(int st, int line)
 {
 #ifdef ALD_EMU
-    if(HC.status == 0 && getenv("ALD_EMU_VERBOSE")) fprintf(stderr, "[emu] graph %d: status %d raised at decomp_device.h:%d\n", HC.g, st, line);
+    if(HC.status == 0 && getenv("ALD_EMU_VERBOSE")) fprintf(stderr, "[emu] graph %d: status %d raised at decomp_device_rows.h:%d\n", HC.g, st, line);
+    if(HC.status == 0 && ald::emu_fail_line) ald::emu_fail_line[HC.g] = line;      // the first exit of this run of the graph (tests/kernel_emu/emu_capi.cc: emu_result_fail_lines)
 #endif
     if(HC.status == 0) HC.status = st;
 }
@@ -1050,7 +1052,7 @@ template<bool A, bool SMALL> ALD_INL void decompose_trivial_star(int x)
     double vwt = C.vx[x].vw; const int lt = uni(C.vx[x].lpos), rt = uni(C.vx[x].rpos), ov = uni(C.vx[x].v2v);
     bool consumed = false;
     for(int q = 0; q < n; q++) {
-        if(consumed) { C.vx[x].vw = vwt; fail(ALD_ST_INVARIANT + ALD_INV_OTHER); return; }     // the general form would be handed a dead edge here
+        if(consumed) { C.vx[x].vw = vwt; fail(ALD_ST_INVARIANT + ALD_INV_DEGREE); return; }     // c is gone and fan edges are left: merge_adjacent_edges returns -1 for each (scallop.cc:2397), then assert(gr.degree(root) == 0) (scallop.cc:2139)
         const int j = ord[q], f = fe[j]; const double ww = fw[j];
         const double wcur = H.ed[c].w;                                   // what is left of c
         const bool sc = uni(!(fabs(wcur - ww) <= kSMIN));                        // split_edge(c, ww) cuts a piece off (scallop.cc:2433-2484)
@@ -1067,7 +1069,10 @@ template<bool A, bool SMALL> ALD_INL void decompose_trivial_star(int x)
         const uint32_t nsf = uni(C.ed[f].sp_len); const int idf = uni(C.ed[f].s0id); const double abf = C.ed[f].s0abd;
         const uint64_t mk0 = C.ed[f].mask[0] | C.ed[c].mask[0];
         PROF_ADD(PF_T_MERGE_LOAD);
-        if(!(cntc > 0 && cntf > 0)) { C.vx[x].vw = vwt; fail(ALD_ST_INVARIANT + ALD_INV_COUNT); return; }
+        if(!(cntc > 0 && cntf > 0)) {      // (an infinite pair weight up to here would have ended the reference in merge_adjacent_equal_edges: fabs(inf - inf) is a NaN, scallop.cc:2242-2378)
+            bool inf_first = false; for(int qq = 0; qq <= q; qq++) if(!(fw[ord[qq]] <= DBL_MAX)) inf_first = true;
+            C.vx[x].vw = vwt; fail(ALD_ST_INVARIANT + (inf_first ? ALD_INV_MERGE_EQUAL : ALD_INV_COUNT)); return;
+        }
         if(nsc == 1 && nsf == 1) {      // one supporting sample on both sides: intersect_samples' inline case, c's half already in registers
             if(idf == idc) { const double xa = A ? abc : abf, ya = A ? abf : abc; const double mn = (ya < xa) ? ya : xa; C.ed[f].sp_off = 0; C.ed[f].ecount = 1; C.ed[f].eabd = 0.0 + mn; C.ed[f].s0abd = mn; }
             else { C.ed[f].sp_off = 0; C.ed[f].sp_len = 0; C.ed[f].ecount = 0; C.ed[f].eabd = 0; C.ed[f].s0id = 0; C.ed[f].s0abd = 0; }
@@ -1114,7 +1119,7 @@ template<bool A, bool SMALL> ALD_INL void decompose_trivial_star(int x)
         for(int q = 0; q < n; q++) { if(A) link_out(far, aux[q]); else link_in(far, aux[q]); }
     }
     if(n >= 2) hs_remove(c);
-    if(ALD_UNLIKELY(!consumed)) { fail(ALD_ST_INVARIANT + ALD_INV_DEGREE); return; }      // c kept a remainder: the reference asserts on the degree of x
+    if(ALD_UNLIKELY(!consumed)) { fail(ALD_ST_INVARIANT + (!(mdc <= DBL_MAX) ? ALD_INV_MERGE_EQUAL : ALD_INV_DEGREE)); return; }      // (an infinite pair weight: the reference's merge-equal assert) c kept a remainder: the reference asserts on the degree of x
     // remove_edge(c); x is left without edges
     if(A) unlink_out(far, c); else unlink_in(far, c);
     H.ed[c].hf = 0; slot_release(c);
@@ -1324,7 +1329,7 @@ template<bool A> ALD_INL void star_wave_body(int x)
         const uint32_t nsf = pf_ns; const int idf = pf_id; const double abf = pf_abd;
         {   // what the sequential form checks when it reaches merge q, in its order: a consumed c, the id counter, the two counts
             int code = 0;
-            if(dead) code = ALD_ST_INVARIANT + ALD_INV_OTHER;
+            if(dead) code = ALD_ST_INVARIANT + ALD_INV_DEGREE;     // (c is gone, fan edges are left: scallop.cc:2397, then the assert of scallop.cc:2139)
             else if(nid - (sc ? 1 : 0) >= EID_LIMIT) code = ALD_ST_CAPACITY;
             else if(!(cntc > 0 && cntf > 0)) code = ALD_ST_INVARIANT + ALD_INV_COUNT;
             inv[q] = code; if(ALD_UNLIKELY(code)) broken = true;
@@ -1351,7 +1356,11 @@ template<bool A> ALD_INL void star_wave_body(int x)
     const bool any_multi = wballot(multi) != 0;
     if(ALD_UNLIKELY(wballot(broken) != 0)) {                                    // the failure the sequence meets first: the smallest q that has one
         wsync();
-        if(lane == 0) for(int q = 0; q < n; q++) if(inv[q]) { fail(inv[q]); break; }
+        if(lane == 0) for(int q = 0; q < n; q++) if(inv[q]) {
+            int code = inv[q];
+            if(code == ALD_ST_INVARIANT + ALD_INV_COUNT) for(int qq = 0; qq <= q; qq++) if(!(fw[ord[qq]] <= DBL_MAX)) code = ALD_ST_INVARIANT + ALD_INV_MERGE_EQUAL;     // (an infinite pair weight in front of it: fabs(inf - inf) is a NaN in merge_adjacent_equal_edges)
+            fail(code); break;
+        }
         wsync();
         return;
     }
@@ -1361,7 +1370,7 @@ template<bool A> ALD_INL void star_wave_body(int x)
     if(lane == 0 && consumed) { if(A) unlink_out(far, c); else unlink_in(far, c); }
     wsync();
     PROF_ADD(PF_T_MERGE_MASK);
-    if(ALD_UNLIKELY(!consumed)) { if(lane == 0) fail(ALD_ST_INVARIANT + ALD_INV_DEGREE); wsync(); return; }     // c kept a remainder: the reference asserts on the degree of x
+    if(ALD_UNLIKELY(!consumed)) { if(lane == 0) fail(ALD_ST_INVARIANT + (!(dctx[0] <= DBL_MAX) ? ALD_INV_MERGE_EQUAL : ALD_INV_DEGREE)); wsync(); return; }     // c kept a remainder: the reference asserts on the degree of x -- or, with an infinite pair weight, in merge_adjacent_equal_edges
     // ---- phase 6: the merged edges enter far's row.  Lane j holds old entry j and its key, lane q merged edge q (merge order) and its
     // key; a merged edge goes behind every old entry whose key does not exceed its own (old entries carry older ids) and among the new
     // ones by (key, creation order): one pass over the new keys gives every old entry its shift and every new one its place, then ALL
@@ -1993,7 +2002,14 @@ ALD_FN int scan_trivial(int start, int mode, int type, double jump_ratio)
         if(need) { if(lane == 0) { HC.sw_dom_base = base; HC.sw_need_lo = (uint32_t)need; HC.sw_need_hi = (uint32_t)(need >> 32); } code = SC_NEED; break; }
         bool cand = (cls == type);
         if(cand) { bool ok; r = compute_balance_ratio(i, ok); if(!ok) bad = true; }
-        if(wballot(bad)) { code = SC_BAD; break; }
+        {   // the reference meets the vertices in order (scallop.cc:1180-1234): a weight sum below SMIN asserts only if no vertex in front of it, in
+            // this chunk, fires `now` or stops the sweep -- that one is taken first, and the scan that follows meets the assert in its turn
+            if(wballot(bad)) {
+                const uint64_t badm = wballot(bad);
+                const uint64_t ev = wballot(cand && !bad && (r < now_thr || (mode == 1 && r < jump_ratio)));
+                if(!(ev & ((1ull << ffs64(badm)) - 1))) { code = SC_BAD; break; }
+            }
+        }
         uint64_t now = wballot(cand && r < now_thr);
         // scallop.cc:1222 `if(ratio < jump_ratio) break;`: the first candidate with 1.02 <= r < jump_ratio becomes the root and ends the sweep
         uint64_t stp = (mode == 1) ? wballot(cand && !(r < now_thr) && r < jump_ratio) : 0ull;
@@ -2146,8 +2162,9 @@ ALD_INL bool sweep_smallest_body(double max_ratio, int &fired, const bool tr)
                 if(c < c0 || c * ALD_WAVE >= vend || hit >= 0 || badw) continue;          // (wave-uniform)
                 const int i = c * ALD_WAVE + lane;
                 const int e = (i >= start && i < vend) ? ce[c] : -1;
-                if(wballot(e == -3)) { badw = true; continue; }
+                const uint64_t badm = wballot(e == -3);
                 const uint64_t now = wballot(e >= 0 && cr[c] < 0.01);
+                if(ALD_UNLIKELY(badm != 0) && (!now || ffs64(badm) < ffs64(now))) { badw = true; continue; }     // (in the reference's order, scallop.cc:844-945: a `now` vertex in front of the assert fires first)
                 if(now) { const int l = ffs64(now); hit = c * ALD_WAVE + l; hit_e = wread(e, l); hit_r = wread(cr[c], l); }
             }
             if(badw) { if(lane == 0) fail(ALD_ST_INVARIANT + ALD_INV_WEIGHT); wsync(); return true; }

@@ -24,6 +24,8 @@ struct GraphResult {
     ora::Census census;
     ora::SweepCensus sweeps;
     int feature_assert = 0;
+    std::string site;                           // the assert the run ended on (ora::site_name), empty: none
+    ora::RuleCtx rule;                          // the vertex of the rule in flight at that moment
 };
 
 struct Packed {
@@ -88,14 +90,14 @@ void run_one(const Packed &P, const Offsets &o, int g, const ora::Params &cfg, b
     try {
         ora::Scallop sc(gr, hs, cfg);
         if(want_trace) sc.trace = &out.trace;
-        sc.census = &out.census; sc.sweeps = &out.sweeps;
+        sc.census = &out.census; sc.sweeps = &out.sweeps; sc.rule = &out.rule;
         sc.assemble();
         out.paths = sc.paths; out.trsts = sc.trsts; out.st = sc.st; out.iterations = sc.st.iterations; out.feature_assert = sc.feature_assert;
         if(sc.st.cut_short) out.status = ALD_ST_SKIPPED_LARGE;        // the loop left through `num_vertices() > max_num_exons` (scallop.cc:49), at the start or after growing
     } catch(const ora::AssertFail &a) {
         out.status = ALD_ST_INVARIANT + a.cls;
-        out.paths.clear(); out.trsts.clear();
-        if(getenv("ORA_VERBOSE")) fprintf(stderr, "oracle: graph %d assert class %d line %d: %s\n", g, a.cls, a.line, a.what);
+        out.paths.clear(); out.trsts.clear(); out.site = ora::site_name(a);
+        if(getenv("ORA_VERBOSE")) fprintf(stderr, "oracle: graph %d assert class %d line %d: %s [%s, vertex %d in %d out %d]\n", g, a.cls, a.line, a.what, out.site.c_str(), out.rule.vertex, out.rule.in_degree, out.rule.out_degree);
     }
 }
 
@@ -260,6 +262,19 @@ int ora_result_sweep_census(const ora_result *R, int32_t graph, int32_t *n_rows,
     return 0;
 }
 
+/* where a graph's run ended on an assert: the site name (scallop_oracle.hpp: site_name; a name, never a line number) and {the vertex the rule in
+ * flight was working on, its in-degree, its out-degree when the rule began} (-1s outside the vertex rules).  Returns 1 and fills both for a graph
+ * that ended on an assert, 0 (empty name, -1s) otherwise, -1 when the name does not fit cap bytes. */
+int ora_result_assert_site(const ora_result *R, int32_t graph, char *site, int32_t cap, int32_t *vertex3)
+{
+    const GraphResult &G = R->gr[graph];
+    if((int)G.site.size() + 1 > cap) return -1;
+    memcpy(site, G.site.c_str(), G.site.size() + 1);
+    const bool hit = !G.site.empty();
+    vertex3[0] = hit ? G.rule.vertex : -1; vertex3[1] = hit ? G.rule.in_degree : -1; vertex3[2] = hit ? G.rule.out_degree : -1;
+    return hit ? 1 : 0;
+}
+
 int ora_result_trace(const ora_result *R, int32_t graph, int32_t *n_events, int32_t *codes3, double *values, int32_t cap)
 {
     const auto &t = R->gr[graph].trace;
@@ -276,8 +291,10 @@ struct ora_staged {
     std::vector<double> edge_weight, edge_abd, sample_abd, vertex_weight; std::vector<uint8_t> edge_strand; char strand = '.';
     std::vector<int32_t> smap, tmap;
 };
+static thread_local std::string g_pre_site;
 int ora_pre_assemble(const ald_graph_view *g, const ald_phase_view *ph, int32_t dist, ora_staged **out)
 {
+    g_pre_site.clear();
     const int V = g->num_vertices, NE = g->num_edges;
     ora::Graph gr; for(int i = 0; i < V; i++) gr.add_vertex();
     gr.strand = g->strand ? g->strand : '.';
@@ -319,10 +336,12 @@ int ora_pre_assemble(const ald_graph_view *g, const ald_phase_view *ph, int32_t 
         for(int i = 0; i < V; i++) { S->vertex_weight.push_back(gr.vwrt[i]); S->vertex_lpos.push_back(gr.vinf[i].lpos); S->vertex_rpos.push_back(gr.vinf[i].rpos); S->vertex_type.push_back(gr.vinf[i].type); }
         S->strand = gr.strand;
         for(auto &x : hx.nodes) { for(int q : x.first) S->phasing_vertex.push_back(q); S->phasing_offset.push_back((int32_t)S->phasing_vertex.size()); S->phasing_count.push_back(x.second); }
-    } catch(const ora::AssertFail &a) { delete S; return ALD_ST_INVARIANT + a.cls; }
+    } catch(const ora::AssertFail &a) { delete S; g_pre_site = ora::site_name(a); return ALD_ST_INVARIANT + a.cls; }
     *out = S;
     return 0;
 }
+/* the site name of the assert the calling thread's last ora_pre_assemble ended on ("" when it went through) */
+const char *ora_pre_assemble_site() { return g_pre_site.c_str(); }
 int ora_staged_view(const ora_staged *S, ald_graph_view *g)
 {
     static const int32_t zi = 0; static const double zd = 0; static const uint8_t zb = 0;

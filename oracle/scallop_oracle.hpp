@@ -51,8 +51,13 @@ enum { TRIVIAL = 0, NORMAL = 1, SPLITTABLE_SIMPLE = 2, SPLITTABLE_HYPER = 3, SPL
        UNSPLITTABLE_SINGLE = 5, UNSPLITTABLE_MULTIPLE = 6, TRIVIAL_VERTEX = 7, SMALLEST_EDGE = 0 }; // util/constants.h:30-46
 static const int EMPTY_VERTEX = -9;            // util/constants.h:53
 
-struct AssertFail { int cls; int line; const char *what; };
-#define ORA_ASSERT(cls, cond) do { if(!(cond)) throw ora::AssertFail{cls, __LINE__, #cond}; } while(0)
+// Every assert has a SITE NAME that survives edits of this file: scope (ORA_SCOPE, set in front of every struct) + function + a tag -- the text of
+// the condition, or a word of its own where one function states the same condition twice.  The line number is kept for messages only.
+struct AssertFail { int cls; int line; const char *what; const char *scope; const char *func; const char *tag; };
+#define ORA_ASSERT_AT(cls, tag, cond) do { if(!(cond)) throw ora::AssertFail{cls, __LINE__, #cond, ORA_SCOPE, __func__, tag}; } while(0)
+#define ORA_ASSERT(cls, cond) ORA_ASSERT_AT(cls, #cond, cond)
+#define ORA_SCOPE ""
+inline std::string site_name(const AssertFail &a) { return std::string(a.scope) + a.func + ": " + a.tag; }
 // assert classes mirror include/aletsch_decomp.h ALD_INV_*
 enum { INV_WEIGHT = 1, INV_MERGE_EQUAL = 2, INV_COUNT = 3, INV_ROUTER = 4, INV_DEGREE = 5, INV_OTHER = 9 };
 
@@ -83,6 +88,8 @@ typedef std::tuple<int, int, int> EKey;        // (source, target, creation id):
 // ---------------------------------------------------------------------------------------------
 // directed graph with the reference's iteration orders (graph/directed_graph.cc, graph_base.cc)
 // ---------------------------------------------------------------------------------------------
+#undef ORA_SCOPE
+#define ORA_SCOPE "Graph::"
 struct Graph {
     std::vector<std::set<EKey>> si, so;        // vertex_base::si / so
     std::set<int> se;                          // graph_base::se  (creation order)
@@ -187,6 +194,8 @@ struct Graph {
 // what assembler::assemble(gx, px, sid) does before it builds the scallop object (meta/assembler.cc:1075-1086)
 // PARITY UNPINNED: splice_graph.cc / graph_reviser.cc / essential.cc need config.h, Boost.ICL and htslib to build
 // ---------------------------------------------------------------------------------------------
+#undef ORA_SCOPE
+#define ORA_SCOPE ""
 inline bool check_continuous_vertices(const Graph &gr, int x, int y) {       // essential.cc:436-446
     if(x >= y) return true;
     for(int i = x; i < y; i++) { if(gr.edge(i, i + 1) < 0) return false; if(gr.vinf[i].rpos != gr.vinf[i + 1].lpos) return false; }
@@ -272,6 +281,8 @@ inline void group_end_boundaries(Graph &gr, std::map<int32_t, int32_t> &tmap, in
         }
     }
 }
+#undef ORA_SCOPE
+#define ORA_SCOPE "PhaseSet::"
 struct PhaseSet {                               // rnacore/phase_set.h:21-32
     std::map<std::vector<int32_t>, int> pmap;
     void add(const std::vector<int32_t> &v, int c) {                                                                    // phase_set.cc:12-25
@@ -290,6 +301,8 @@ struct PhaseSet {                               // rnacore/phase_set.h:21-32
         pmap = std::move(ps.pmap);
     }
 };
+#undef ORA_SCOPE
+#define ORA_SCOPE ""
 inline bool build_path_from_exon_coordinates(const Graph &gr, const std::map<int32_t, int> &lindex, const std::map<int32_t, int> &rindex,
                                              const std::vector<int32_t> &v, std::vector<int> &vv) {                     // essential.cc:321-366
     vv.clear();
@@ -323,6 +336,8 @@ inline bool check_valid_path(const Graph &gr, const std::vector<int> &vv) {     
     return true;
 }
 
+#undef ORA_SCOPE
+#define ORA_SCOPE "HyperSet::"
 struct HyperSet {
     std::map<std::vector<int>, int> nodes;      // MVII nodes (after ctor + filter_nodes: boundary input)
     HyperSet() {}
@@ -516,6 +531,8 @@ struct HyperSet {
 // ---------------------------------------------------------------------------------------------
 // small undirected multigraph with the reference's orders (graph/undirected_graph.cc)
 // ---------------------------------------------------------------------------------------------
+#undef ORA_SCOPE
+#define ORA_SCOPE "UGraph::"
 struct UGraph {
     std::vector<std::set<EKey>> so;
     std::set<int> se; std::vector<int> es, et;
@@ -563,6 +580,8 @@ typedef std::map<std::pair<int, int>, int> MPII;
 // ---------------------------------------------------------------------------------------------
 // router (scallop/router.cc): live part = classify_plain_vertex + thread
 // ---------------------------------------------------------------------------------------------
+#undef ORA_SCOPE
+#define ORA_SCOPE "Router::"
 struct Router {
     int root; Graph &gr; const Params &cfg;
     std::vector<std::pair<int, int>> routes; std::vector<int> counts;
@@ -789,6 +808,11 @@ struct SweepCand { int v; double r; bool now; };
 // ---------------------------------------------------------------------------------------------
 // scallop (scallop/scallop.cc)
 // ---------------------------------------------------------------------------------------------
+// the vertex the rule in flight works on and its degrees when the rule began (kept by the caller: it outlives a run that ends on an assert);
+// -1: no vertex rule in flight (the collect / greedy phase)
+struct RuleCtx { int vertex = -1, in_degree = -1, out_degree = -1; };
+#undef ORA_SCOPE
+#define ORA_SCOPE "Scallop::"
 struct Scallop {
     const Params &cfg; Graph &gr; HyperSet &hs;
     std::vector<std::vector<int>> mev; std::vector<double> med; std::vector<int> mei;
@@ -796,6 +820,8 @@ struct Scallop {
     std::vector<Path> paths; std::vector<Transcript> trsts;
     std::vector<TraceEvent> *trace = nullptr; Stats st; Census *census = nullptr;        // where the caller wants the census (it outlives a run that ends on an assert)
     SweepCensus *sweeps = nullptr;              // likewise, the census of the sweeps
+    RuleCtx *rule = nullptr;                    // likewise, the vertex of the rule in flight
+    void at(int v) { if(rule) { if(v < 0) *rule = RuleCtx(); else *rule = RuleCtx{v, gr.in_degree(v), gr.out_degree(v)}; } }
     Graph gr_ori;
     int feature_assert = 0;                     // line of the first assert update_trst_features would have hit (0: none); the paths stand either way
 
@@ -829,6 +855,7 @@ struct Scallop {
             break;
         }
         track();
+        at(-1);
         collect_existing_st_paths();
         greedy_decompose();
         track();
@@ -978,6 +1005,7 @@ struct Scallop {
         for(int i : vv) {
             if(gr.in_degree(i) <= 1) continue;
             if(gr.out_degree(i) <= 1) continue;
+            at(i);
             double r; int e = compute_smallest_edge(i, r);
             if(e == -1) continue;
             int s = gr.es[e], t = gr.et[e];
@@ -1014,6 +1042,7 @@ struct Scallop {
         for(int i : vv) {
             if(gr.in_degree(i) <= 1) continue;
             if(gr.out_degree(i) <= 1) continue;
+            at(i);
             MPII mpi = hs.get_routes(i, gr);
             Router rt(i, gr, mpi, cfg);
             rt.classify();
@@ -1038,12 +1067,13 @@ struct Scallop {
     }
 
     void decompose_vertex_extend(int root, MPID &pe2w) {   // scallop.cc:1675-1986
+        at(root);
         std::map<int, int> mdegree;
         for(auto &kv : pe2w) { mdegree[kv.first.first]++; mdegree[kv.first.second]++; }
         double total_weight = 0; std::map<int, double> mweight;
         for(auto &kv : pe2w) {
             double w = kv.second;
-            ORA_ASSERT(INV_WEIGHT, w >= cfg.min_guaranteed_edge_weight - SMIN);
+            ORA_ASSERT_AT(INV_WEIGHT, "pair weight, totals", w >= cfg.min_guaranteed_edge_weight - SMIN);
             total_weight += w;
             if(!mweight.count(kv.first.first)) mweight[kv.first.first] = w; else mweight[kv.first.first] += w;
             if(!mweight.count(kv.first.second)) mweight[kv.first.second] = w; else mweight[kv.first.second] += w;
@@ -1074,7 +1104,7 @@ struct Scallop {
         }
         for(auto &kv : pe2w) {
             int e1 = kv.first.first, e2 = kv.first.second; double w = kv.second;
-            ORA_ASSERT(INV_WEIGHT, w >= cfg.min_guaranteed_edge_weight - SMIN);
+            ORA_ASSERT_AT(INV_WEIGHT, "pair weight, relink", w >= cfg.min_guaranteed_edge_weight - SMIN);
             if(mdegree[e1] == 1 && mdegree[e2] >= 2) {
                 ORA_ASSERT(INV_OTHER, !ev1.count(e1) && ev2.count(e2));
                 borrow_edge_strand(e1, e2);
@@ -1123,6 +1153,7 @@ struct Scallop {
         ORA_ASSERT(INV_DEGREE, gr.degree(old_sink) == 0);
     }
     void decompose_vertex_replace(int root, MPID &pe2w) {  // scallop.cc:2009-2142
+        at(root);
         std::map<int, double> md;
         for(auto &kv : pe2w) {
             double w = kv.second;
@@ -1157,6 +1188,7 @@ struct Scallop {
         (*census)[{1, gr.in_degree(x), gr.out_degree(x), hs.edges.empty() ? 0 : 1, single ? 1 : 0, zero ? 1 : 0}]++;
     }
     void decompose_trivial_vertex(int x) {      // scallop.cc:2144-2167
+        at(x);
         if(census) { if(gr.in_degree(x) == 1) (*census)[{0, 0, gr.out_degree(x), 0, 0, 0}]++; else (*census)[{0, 1, gr.in_degree(x), 0, 0, 0}]++; }
         balance_vertex(x);
         MPID pe2w;
@@ -1237,8 +1269,8 @@ struct Scallop {
         std::vector<int> ve1 = gr.in_edges(v), ve2 = gr.out_edges(v);
         if(gr.degree(v) <= 0 || ve1.empty() || ve2.empty()) return;
         double w1 = 0, w2 = 0;
-        for(int e : ve1) { double w = gr.ewrt[e]; ORA_ASSERT(INV_WEIGHT, w >= cfg.min_guaranteed_edge_weight - SMIN); w1 += w; }
-        for(int e : ve2) { double w = gr.ewrt[e]; ORA_ASSERT(INV_WEIGHT, w >= cfg.min_guaranteed_edge_weight - SMIN); w2 += w; }
+        for(int e : ve1) { double w = gr.ewrt[e]; ORA_ASSERT_AT(INV_WEIGHT, "in-edge weight", w >= cfg.min_guaranteed_edge_weight - SMIN); w1 += w; }
+        for(int e : ve2) { double w = gr.ewrt[e]; ORA_ASSERT_AT(INV_WEIGHT, "out-edge weight", w >= cfg.min_guaranteed_edge_weight - SMIN); w2 += w; }
         double ww = sqrt(w1 * w2);
         double r1 = ww / w1, r2 = ww / w2;
         double m1 = 0, m2 = 0;

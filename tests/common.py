@@ -97,6 +97,46 @@ def oracle_run(pg: PackedGraphs, threads: int = 1, trace: bool = False, params=N
     return r, st, sec, traces
 
 
+def oracle_assert_sites(pg: PackedGraphs, threads: int = 1, params=None):
+    """where every graph's run in the oracle ended on an assert -> (DecompResult, op traces, [None | (site name, vertex of the rule in flight,
+    its in-degree, its out-degree when the rule began)]); the site is a NAME (scope + function + tag: oracle/scallop_oracle.hpp site_name)"""
+    O = oracle_lib()
+    O.ora_result_assert_site.argtypes = [C.c_void_p, C.c_int32, C.c_char_p, C.c_int32, C.POINTER(C.c_int32)]
+    h = C.c_void_p()
+    rc = O.ora_run_packed(*pg.c_args(), C.byref(params) if params is not None else None, C.c_int32(threads), C.c_int32(1), C.byref(h))
+    assert rc == 0
+    r = export_via(O.ora_result_export, h, pg.n)
+    sites, traces = [], []
+    buf = C.create_string_buffer(256); v3 = (C.c_int32 * 3)()
+    for g in range(pg.n):
+        hit = O.ora_result_assert_site(h, g, buf, 256, v3)
+        assert hit >= 0
+        sites.append((buf.value.decode(), int(v3[0]), int(v3[1]), int(v3[2])) if hit else None)
+        n = C.c_int32()
+        O.ora_result_trace(h, g, C.byref(n), None, None, 0)
+        codes = np.zeros(3 * max(n.value, 1), np.int32); vals = np.zeros(max(n.value, 1))
+        O.ora_result_trace(h, g, C.byref(n), codes.ctypes.data_as(C.POINTER(C.c_int32)), vals.ctypes.data_as(C.POINTER(C.c_double)), n.value)
+        traces.append([(int(codes[3 * i]), int(codes[3 * i + 1]), int(codes[3 * i + 2]), float(vals[i])) for i in range(n.value)])
+    O.ora_result_free(h)
+    return r, traces, sites
+
+
+def emu_run_full(pg: PackedGraphs, params=None, rows: bool = False, keep: bool = False, cap: int = 1 << 13, force_class: int = 0):
+    """one run of the emulation -> (DecompResult, iterations[n], class[n], op traces, line[n]); line: the source line of the engine header whose
+    fail() set the graph's status in the attempt that counts (0: none) -- emulation builds only, the device build has no such word"""
+    E = emu_rows_lib() if rows else (emu_keep_lib() if keep else emu_lib())
+    h = C.c_void_p()
+    rc = E.emu_run_packed(*pg.c_args(), C.byref(params) if params is not None else None, C.c_int32(cap), C.c_int32(force_class), C.byref(h))
+    assert rc == 0, rc
+    r = export_via(E.emu_result_export, h, pg.n)
+    it = np.zeros(pg.n, np.int32); cl = np.zeros(pg.n, np.int32); ln = np.zeros(pg.n, np.int32)
+    E.emu_result_iters(h, it.ctypes.data_as(C.POINTER(C.c_int32)), cl.ctypes.data_as(C.POINTER(C.c_int32)))
+    E.emu_result_fail_lines(h, ln.ctypes.data_as(C.POINTER(C.c_int32)))
+    traces = [emu_trace_of(E, h, g, cap) for g in range(pg.n)]
+    E.emu_result_free(h)
+    return r, it, cl, traces, ln
+
+
 def oracle_transcripts(pg: PackedGraphs):
     """coverage + exon lists per path (scallop.cc:3250-3266, essential.cc:719-748) from the oracle."""
     O = oracle_lib()
@@ -149,9 +189,11 @@ def emu_run_raw(items, params=None, force_class: int = 0, trace_cap: int = 0, fu
         it = np.zeros(len(items), np.int32); cl = np.zeros(len(items), np.int32)
         E.emu_result_iters(h, it.ctypes.data_as(C.POINTER(C.c_int32)), cl.ctypes.data_as(C.POINTER(C.c_int32)))
         traces = [emu_trace_of(E, h, g, trace_cap) for g in range(len(items))] if trace_cap > 0 else None
+        ln = np.zeros(len(items), np.int32); E.emu_result_fail_lines(h, ln.ctypes.data_as(C.POINTER(C.c_int32)))
         E.emu_result_free(h)
     finally:
         E.emu_batch_free(B)
+    if full == "lines": return r, it, cl, traces, ln           # (+ the source line of the fail() behind every status: emu_run_full)
     return (r, it, cl, traces) if full else (r, it)
 
 
@@ -189,6 +231,20 @@ def emu_transcripts(pg: PackedGraphs):
     E.emu_result_export_transcripts(h, C.byref(te), cov.ctypes.data_as(C.POINTER(C.c_double)), eo.ctypes.data_as(C.POINTER(C.c_int64)), lr.ctypes.data_as(C.POINTER(C.c_int32)))
     E.emu_result_free(h)
     return r, cov, eo, lr[:2 * te.value].reshape(-1, 2)
+
+
+def select_results(r, keep):
+    """the results of graphs `keep` (ascending) as a DecompResult of their own"""
+    from aletsch_amd.packed import DecompResult
+    po = r.path_offset; pv = r.pv_offset
+    paths = np.concatenate([np.arange(po[g], po[g + 1]) for g in keep]) if len(keep) else np.zeros(0, np.int64)
+    cnt = np.array([po[g + 1] - po[g] for g in keep], np.int64)
+    new_po = np.concatenate([[0], np.cumsum(cnt)]).astype(r.path_offset.dtype)
+    lens = (pv[paths + 1] - pv[paths]) if len(paths) else np.zeros(0, np.int64)
+    new_pv = np.concatenate([[0], np.cumsum(lens)]).astype(r.pv_offset.dtype)
+    verts = np.concatenate([r.path_vertices[pv[p]:pv[p + 1]] for p in paths]) if len(paths) else np.zeros(0, r.path_vertices.dtype)
+    return DecompResult(status=r.status[keep], path_offset=new_po, weight=r.weight[paths], abd=r.abd[paths], conf=r.conf[paths], reads=r.reads[paths],
+                        length=r.length[paths], count=r.count[paths], strand=r.strand[paths], pv_offset=new_pv, path_vertices=verts)
 
 
 def compare_results(want: DecompResult, got: DecompResult, n: int, tol: float = 0.0, conf_tol: float = 0.0):

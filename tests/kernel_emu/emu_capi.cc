@@ -7,6 +7,8 @@
 #include "../../aletsch_amd/csrc/host_pack.h"
 #include <cstdlib>
 
+namespace ald { inline int32_t *emu_fail_line = nullptr; }      // written by fail_() of the engine headers (emulation only)
+
 extern "C" {
 #define ALD_DECL(ID) void emu_run_class_##ID(const ald::KernelArgs *);
 ALD_FOR_EACH_PICK_CLASS(ALD_DECL)
@@ -15,7 +17,7 @@ ALD_DECL(13)
 }
 using namespace ald;
 
-struct emu_result { HostResults R; int n = 0; std::vector<int32_t> trace_n, trace_codes; std::vector<double> trace_vals; int trace_cap = 0; std::vector<int32_t> cls; };
+struct emu_result { HostResults R; int n = 0; std::vector<int32_t> trace_n, trace_codes; std::vector<double> trace_vals; int trace_cap = 0; std::vector<int32_t> cls, fail_line; };
 
 extern "C" {
 
@@ -66,6 +68,7 @@ static int emu_run_batch(HostBatch &B, const ald_params *prm, int32_t trace_cap,
     std::vector<int32_t> work[ALD_NUM_CLASSES];
     std::fill(status.begin(), status.end(), 0); std::fill(n_paths.begin(), n_paths.end(), 0); std::fill(attempt.begin(), attempt.end(), 0); pool_used = 0; index_used = 0; std::fill(graph_first.begin(), graph_first.end(), -1);
     if(trace_cap > 0) std::fill(E->trace_n.begin(), E->trace_n.end(), 0);
+    E->fail_line.assign(n, 0); ald::emu_fail_line = E->fail_line.data();
     for(int g = 0; g < n; g++) {
         int64_t ns = B.off_s[g + 1] - B.off_s[g], npv = B.off_pv[g + 1] - B.off_pv[g];
         if(B.g_rawdist[g] >= 0) npv += 2 * (B.off_rc[g + 1] - B.off_rc[g]);
@@ -92,7 +95,7 @@ static int emu_run_batch(HostBatch &B, const ald_params *prm, int32_t trace_cap,
         for(int c = 0; c < ALD_NUM_CLASSES; c++) for(int g : work[c]) {
             attempt[g] = pass;
             const int up = class_retry_up(c);
-            if(status[g] == ALD_ST_CAPACITY && up >= 0) { cls[g] = up; next[up].push_back(g); }
+            if(status[g] == ALD_ST_CAPACITY && up >= 0) { cls[g] = up; next[up].push_back(g); E->fail_line[g] = 0; }      // (the line of the attempt that counts)
         }
         for(int c = 0; c < ALD_NUM_CLASSES; c++) work[c].swap(next[c]);
     }
@@ -102,6 +105,7 @@ static int emu_run_batch(HostBatch &B, const ald_params *prm, int32_t trace_cap,
     A.out.pool = pool.data(); A.out.pool_cap = pool_cap;
     index_cap = pool_cap / (ALD_REC_HDR + 2) + 1; index.assign(index_cap, 0); A.out.index = index.data(); A.out.index_cap = index_cap;
   }
+    ald::emu_fail_line = nullptr;
     E->R.status = status; E->R.n_iters = n_iters;
     E->R.pool.assign(pool.begin(), pool.begin() + std::min<uint64_t>(pool_used, pool_cap));
     E->cls = cls;
@@ -139,6 +143,9 @@ int emu_result_trace(const emu_result *E, int32_t graph, int32_t *n_events, int3
     for(int i = 0; i < n && i < cap && i < E->trace_cap; i++) { size_t o = (size_t)graph * E->trace_cap + i; codes3[3 * i] = E->trace_codes[3 * o]; codes3[3 * i + 1] = E->trace_codes[3 * o + 1]; codes3[3 * i + 2] = E->trace_codes[3 * o + 2]; values[i] = E->trace_vals[o]; }
     return 0;
 }
+/* per graph: the line of the engine header (decomp_device.h, or decomp_device_rows.h in the row build) whose fail() set the graph's status in
+ * its last attempt; 0 for a graph without a status the kernel raised */
+int emu_result_fail_lines(const emu_result *E, int32_t *lines) { for(int g = 0; g < E->n; g++) lines[g] = E->fail_line[g]; return 0; }
 void emu_result_free(emu_result *E) { delete E; }
 
 } // extern "C"

@@ -94,18 +94,7 @@ def test_pre_steps_in_the_load_phase_of_the_engine():
     assert np.array_equal(it[ok][good], st[good, 3]) and good.sum() > 150
 
 
-def common_select_results(r, keep):
-    """the results of graphs `keep` (ascending) as a DecompResult of their own"""
-    from aletsch_amd.packed import DecompResult
-    po = r.path_offset; pv = r.pv_offset
-    paths = np.concatenate([np.arange(po[g], po[g + 1]) for g in keep]) if len(keep) else np.zeros(0, np.int64)
-    cnt = np.array([po[g + 1] - po[g] for g in keep], np.int64)
-    new_po = np.concatenate([[0], np.cumsum(cnt)]).astype(r.path_offset.dtype)
-    lens = (pv[paths + 1] - pv[paths]) if len(paths) else np.zeros(0, np.int64)
-    new_pv = np.concatenate([[0], np.cumsum(lens)]).astype(r.pv_offset.dtype)
-    verts = np.concatenate([r.path_vertices[pv[p]:pv[p + 1]] for p in paths]) if len(paths) else np.zeros(0, r.path_vertices.dtype)
-    return DecompResult(status=r.status[keep], path_offset=new_po, weight=r.weight[paths], abd=r.abd[paths], conf=r.conf[paths], reads=r.reads[paths],
-                        length=r.length[paths], count=r.count[paths], strand=r.strand[paths], pv_offset=new_pv, path_vertices=verts)
+common_select_results = common.select_results          # (the helper lives in common.py; the name stays for the modules that import it from here)
 
 
 def test_pre_steps_by_hand():
