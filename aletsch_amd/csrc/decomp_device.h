@@ -54,10 +54,12 @@ namespace ald { inline int32_t *emu_fail_line = nullptr; }      // emulation onl
 namespace ALD_CLASS_NS {
 using namespace ald;
 #ifdef ALD_EMU_COUNT
-static long g_cnt_router = 0, g_cnt_unsweep = 0, g_cnt_star[34] = {0}, g_cnt_rdeg[34] = {0}, g_cnt_build = 0, g_cnt_pre[3] = {0}, g_cnt_fix[8] = {0}, g_cnt_fix_declined = 0;
+static long g_cnt_router = 0, g_cnt_unsweep = 0, g_cnt_star[34] = {0}, g_cnt_rdeg[34] = {0}, g_cnt_build = 0, g_cnt_pre[3] = {0}, g_cnt_fix[8] = {0}, g_cnt_fix_declined = 0, g_cnt_x22[3] = {0}, g_cnt_x22s[5] = {0};   // x22: extends taken by / declined by the fixed 2 x 2 form, all extends; x22s: in the fixed form, i' borrowed o*'s strand, o' borrowed i*'s, the new edge took i*'s (o* has none), took o*'s over an unstranded i*, hs_insert_between acted
 struct CntPrinter { ~CntPrinter() { if(g_cnt_unsweep) { fprintf(stderr, "[emu-count] class %d: unsplittable sweeps %ld router runs %ld (of which reach build(): %ld; prepared at level 0/1/2: %ld %ld %ld)\n", ALD_CLASS_ID, g_cnt_unsweep, g_cnt_router, g_cnt_build, g_cnt_pre[0], g_cnt_pre[1], g_cnt_pre[2]);
     fprintf(stderr, "[emu-count]   stars by fan size:"); for(int i = 0; i < 34; i++) if(g_cnt_star[i]) fprintf(stderr, " %d:%ld", i, g_cnt_star[i]); fprintf(stderr, "\n");
     fprintf(stderr, "[emu-count]   stars through the fixed-size form:"); for(int i = 0; i < 8; i++) if(g_cnt_fix[i]) fprintf(stderr, " %d:%ld", i, g_cnt_fix[i]); fprintf(stderr, " declined:%ld\n", g_cnt_fix_declined);
+    fprintf(stderr, "[emu-count]   extends: %ld through the fixed 2x2 form: %ld declined: %ld\n", g_cnt_x22[2], g_cnt_x22[0], g_cnt_x22[1]);
+    fprintf(stderr, "[emu-count]   fixed 2x2 form: strand to i' from o*: %ld to o' from i*: %ld to z from i*: %ld to z from o*: %ld insert_between acted: %ld\n", g_cnt_x22s[0], g_cnt_x22s[1], g_cnt_x22s[2], g_cnt_x22s[3], g_cnt_x22s[4]);
     fprintf(stderr, "[emu-count]   router runs by degree:"); for(int i = 0; i < 34; i++) if(g_cnt_rdeg[i]) fprintf(stderr, " %d:%ld", i, g_cnt_rdeg[i]); fprintf(stderr, "\n"); } } }; static CntPrinter g_cnt_printer;
 #endif
 
@@ -2015,6 +2017,200 @@ ALD_INL void decompose_vertex_extend(int root, int n)
     if(uni(HC.pw_lds) != 0 && 4 * deg <= ARENA_I && deg <= ARENA_D && !(uni(HC.p_ratio[7]) > 1.0)) decompose_vertex_extend_small(root, n);
     else decompose_vertex_extend_any(root, n);
 }
+// ---------------------------------------------------------------------------------------------------------------------------------
+// The same decomposition written for ONE shape: a root with two in-edges, two out-edges and three pairs (97 % of the extends of the
+// bench workload; an exon with two junctions on either side).  Three distinct pairs of a 2 x 2 grid always have this form: one in-edge
+// i* and one out-edge o* occur twice, the others (i', o') once -- (i*,o*), (i*,o'), (i',o*); the pair that is missing names i' and o'.
+// What the generic form does with it (scallop.cc:1675-1986), in its own words: i* gets the new vertex m = nv, o* the new vertex m + 1
+// (local order: in-edges first); i* moves to (s(i*), m), o* to (m + 1, t(o*)), i' to (s(i'), m + 1), o' to (m, t(o')); the pair (i*,o*)
+// becomes ONE new edge z = (m, m + 1); the root ends empty.  Eighteen list walks on lane 0 there.  Here:
+//   * every lane gathers the four edges and the three pairs and runs the numeric part on named values (pair order: total_weight
+//     = ((0 + w0) + w1) + w2, each share = w / total_weight * vertex_weight -- the operations of the generic form, same operands, same order);
+//   * lane j (j < 4: in-edges, then out-edges, list order) finishes edge j: its endpoint, its cold record (asked for at the top, the
+//     round trip runs under the arithmetic), its place in the list of its FAR endpoint (relink_out_lane / relink_in_lane: four
+//     different lists, walked at once), its link in the list of its new vertex -- which follows from keys in registers: in(m) = [i*],
+//     in(m + 1) = [i', z] (s(i') < m), out(m + 1) = [o*], out(m) = [o', z], or [z, o'] when o' ends in the sink (which sorts last);
+//   * lane 0 then takes z's slot and id as add_edge_i does, writes z, the two vertex records and the context words, and runs what is
+//     inherently ordered with the existing routines: a multi-sample intersection through the pool, hs_insert_between.
+// In a far list a moved edge keeps its id and takes the new vertex as key; no other entry of that list has this key, so its place is
+// behind every entry with a smaller key, whatever the ids.  Two in-edges from one source (or two out-edges to one target) share their far
+// list: those two moves (endpoint, then the walk) are done on lane 0 in the tail, one after the other, with the scalar routines.  A far list that is only counted
+// (out(source) / in(sink) before special_linked) is left alone by relink_*_lane itself, as the generic form leaves it (-1 + 1).
+// Anything out of the ordinary -- jump_ratio > 1, pairs in the slab, a pair weight below min_w, a zero count, an empty or unallocatable
+// sample intersection, no free slot, no room for two vertices, an exhausted id space, an inconsistent list or pair -- is detected
+// BEFORE the first write and makes the form decline (false): the caller runs the generic form, which treats or reports it as before.
+// -DALD_NO_EXTEND22: the form is not compiled and every extend takes the generic form, as in the parent -- the same results, NOT the
+// parent's kernel: the sweep keeps the call structure of this build.  A timing A/B against the parent uses a build of the parent commit
+// (make VARIANT=parent in a checkout of it), never this switch.
+#ifndef ALD_NO_EXTEND22
+// would intersect_samples(e1, e2, .) allocate and leave at least one sample?  (read-only; the rare multi-sample case)
+ALD_FN bool intersect_would_hold(int e1, int e2)
+{
+    e1 = uni(e1); e2 = uni(e2);
+    COLD;
+    const uint32_t n1 = uni(C.ed[e1].sp_len), n2 = uni(C.ed[e2].sp_len);
+    const int i1 = uni(C.ed[e1].s0id), i2 = uni(C.ed[e2].s0id);
+    if(n1 == 1 && n2 == 1) return i1 == i2;
+    const uint32_t o1 = uni(C.ed[e1].sp_off), o2 = uni(C.ed[e2].sp_off);
+    const uint32_t need = n1 < n2 ? n1 : n2;
+    if(uni(HC.sp_used) + need > C.sp_cap) return false;
+    uint32_t i = 0, j = 0, k = 0;
+    while(i < n1 && j < n2) {
+        int a = n1 == 1 ? i1 : uni(C.sp_id[o1 + i]), b = n2 == 1 ? i2 : uni(C.sp_id[o2 + j]);
+        if(a < b) i++; else if(b < a) j++; else { k++; i++; j++; }
+    }
+    return k > 0;
+}
+ALD_FN bool extend_22(int root)
+{
+    root = uni(root);
+    COLD;
+    const int lane = lane_id();
+    int bad = 0;
+    if(uni(HC.pw_lds) == 0 || uni(HC.p_ratio[7]) > 1.0) bad = 1;
+    // ---- the four edges in local order (in-edges, then out-edges) and their far endpoints
+    const Hot::VertexHot vrx = H.vx[root];
+    int ge[4], gfar[4];
+    {
+        int e = slot_or_neg(vrx.in_head);
+        ALD_UNROLL for(int k = 0; k < 2; k++) {
+            if(e < 0) bad = 1;
+            const int es = e >= 0 ? e : 0; const uint64_t lw = *(const uint64_t*)&H.ed[es].lk;
+            ge[k] = es; gfar[k] = (int)(lw & 0xFFFF); e = lk_next((uint32_t)((lw >> 32) & 0xFFFF));
+        }
+        if(e >= 0) bad = 1;
+        e = slot_or_neg(vrx.out_head);
+        ALD_UNROLL for(int k = 2; k < 4; k++) {
+            if(e < 0) bad = 1;
+            const int es = e >= 0 ? e : 0; const uint64_t lw = *(const uint64_t*)&H.ed[es].lk;
+            ge[k] = es; gfar[k] = (int)((lw >> 16) & 0xFFFF); e = lk_next((uint32_t)(lw >> 48));
+        }
+        if(e >= 0) bad = 1;
+    }
+    // the root's record (one broadcast request) and, lane j, the record of edge j and the position of its far vertex
+    const int lt_v = C.vx[root].lpos, rt_v = C.vx[root].rpos, rv_v = C.vx[root].v2v; const double vw_v = C.vx[root].vw;
+#ifndef ALD_EMU
+    double pf_med, pf_abd; int pf_mei, pf_st, pf_cnt, pf_id, pf_pos; uint32_t pf_ns; uint64_t pf_mask0;
+    { const int l4 = lane < 4 ? lane : 0; const int f = pick<4>(ge, l4), fv = pick<4>(gfar, l4);
+      pf_med = C.ed[f].med; pf_abd = C.ed[f].s0abd; pf_mei = C.ed[f].mei; pf_st = C.ed[f].estrand; pf_cnt = C.ed[f].ecount; pf_id = C.ed[f].s0id; pf_ns = C.ed[f].sp_len; pf_mask0 = C.ed[f].mask[0];
+      pf_pos = l4 < 2 ? C.vx[fv].rpos : C.vx[fv].lpos; }
+#endif
+    // ---- the three pairs (sort_pairs order): which edge occurs twice on either side
+    const Pairs P = pairs_at(true, false);
+    const int a0 = P.a[0], a1 = P.a[1], a2 = P.a[2], b0 = P.b[0], b1 = P.b[1], b2 = P.b[2];
+    const double w0 = P.w[0], w1 = P.w[1], w2 = P.w[2];
+    const int la0 = PLOC(a0), la1 = PLOC(a1), la2 = PLOC(a2), lb0 = PLOC(b0) - 2, lb1 = PLOC(b1) - 2, lb2 = PLOC(b2) - 2;
+    if((unsigned)la0 > 1u || (unsigned)la1 > 1u || (unsigned)la2 > 1u || (unsigned)lb0 > 1u || (unsigned)lb1 > 1u || (unsigned)lb2 > 1u) bad = 1;
+    if(PSLOT(a0) != (la0 ? ge[1] : ge[0]) || PSLOT(a1) != (la1 ? ge[1] : ge[0]) || PSLOT(a2) != (la2 ? ge[1] : ge[0])) bad = 1;
+    if(PSLOT(b0) != (lb0 ? ge[3] : ge[2]) || PSLOT(b1) != (lb1 ? ge[3] : ge[2]) || PSLOT(b2) != (lb2 ? ge[3] : ge[2])) bad = 1;
+    const int c0 = uni((la0 << 1) | lb0), c1 = uni((la1 << 1) | lb1), c2 = uni((la2 << 1) | lb2);       // a pair as a cell of the 2 x 2 grid
+    if(c0 == c1 || c0 == c2 || c1 == c2) bad = 1;
+    const int cm = (6 - c0 - c1 - c2) & 3;                                   // the missing cell: (i', o')
+    const int ip = cm >> 1, op = 2 + (cm & 1), is = 1 - ip, os = 5 - op;     // local indices (= lanes) of i', o', i*, o*
+    const int cz = (is << 1) | (os - 2), ci = (ip << 1) | (os - 2), co = (is << 1) | (op - 2);      // cells of (i*,o*), (i',o*), (i*,o')
+    const double mw = HC.p_min_w;
+    if(!(w0 >= mw - kSMIN) || !(w1 >= mw - kSMIN) || !(w2 >= mw - kSMIN)) bad = 1;
+    double total_weight = 0; total_weight += w0; total_weight += w1; total_weight += w2;
+    const double wz = c0 == cz ? w0 : (c1 == cz ? w1 : w2), wi = c0 == ci ? w0 : (c1 == ci ? w1 : w2), wo = c0 == co ? w0 : (c1 == co ? w1 : w2);
+    // ---- capacity: two vertices, one slot (free list first, as add_edge_i), one id
+    const int m = uni(HC.nv), fh = uni(HC.free_head), hw = uni(HC.slot_hw), id = uni(HC.next_id);
+    if(m + 2 > MAXV || (fh < 0 && hw >= MAXE) || id >= EID_LIMIT) bad = 1;
+    const int z = fh >= 0 ? fh : (hw < MAXE ? hw : 0);
+    // ---- parallel edges share a far list
+    const bool dupi = uni(gfar[0] == gfar[1]), dupo = uni(gfar[2] == gfar[3]);
+    // (the loads have had their time)
+    const int rlen = uni(rt_v) - uni(lt_v), rv = uni(rv_v);
+    const double vertex_weight = uni(vw_v) * rlen;
+#ifdef ALD_EMU
+    const int e_is = ge[is], e_os = ge[os], e_ip = ge[ip], e_op = ge[op];
+    const int st_is = C.ed[e_is].estrand, st_os = C.ed[e_os].estrand, cnt_is = C.ed[e_is].ecount, cnt_os = C.ed[e_os].ecount, id_is = C.ed[e_is].s0id, id_os = C.ed[e_os].s0id;
+    const uint32_t ns_is = C.ed[e_is].sp_len, ns_os = C.ed[e_os].sp_len; const double abd_is = C.ed[e_is].s0abd, abd_os = C.ed[e_os].s0abd;
+#else
+    const int e_is = uni(pick<4>(ge, is)), e_os = uni(pick<4>(ge, os)), e_ip = uni(pick<4>(ge, ip)), e_op = uni(pick<4>(ge, op));
+    const int st_is = wread(pf_st, is), st_os = wread(pf_st, os), cnt_is = wread(pf_cnt, is), cnt_os = wread(pf_cnt, os), id_is = wread(pf_id, is), id_os = wread(pf_id, os);
+    const uint32_t ns_is = (uint32_t)wread((int)pf_ns, is), ns_os = (uint32_t)wread((int)pf_ns, os); const double abd_is = wread(pf_abd, is), abd_os = wread(pf_abd, os);
+#endif
+    if(!(cnt_is > 0 && cnt_os > 0)) bad = 1;
+    const bool inline_sp = (ns_is == 1 && ns_os == 1);
+    if(inline_sp) { if(id_is != id_os) bad = 1; }                            // an empty intersection: the generic form reports the zero count
+    else if(!bad && !uni(intersect_would_hold(e_is, e_os))) bad = 1;
+    const bool zfirst = uni(pick<4>(gfar, op) == uni(HC.sinkp));               // o' ends in the sink: z = (m, m + 1) sorts in front of it in out(m)
+    // ---- the decision: nothing has been written so far
+#ifdef ALD_EMU_COUNT
+    if(bad) g_cnt_x22[1]++; else { g_cnt_x22[0]++; if(st_os != 0) g_cnt_x22s[0]++; if(st_is != 0) g_cnt_x22s[1]++; if(st_os == 0 && st_is != 0) g_cnt_x22s[2]++; if(st_os != 0 && st_is == 0) g_cnt_x22s[3]++; }
+#endif
+    if(wballot(bad != 0) != 0) return false;
+    // ---- lane j: edge j
+    for(int j = lane; j < 4; j += ALD_WAVE) {
+        const bool in_side = j < 2, star = (j == is) || (j == os);
+        const int e = pick<4>(ge, j), fv = pick<4>(gfar, j);
+        const int nvx = in_side ? (star ? m : m + 1) : (star ? m + 1 : m);     // the new vertex at its near end
+#ifdef ALD_EMU
+        const double pf_med = C.ed[e].med; const int pf_mei = C.ed[e].mei, pf_pos = in_side ? C.vx[fv].rpos : C.vx[fv].lpos; const uint64_t pf_mask0 = C.ed[e].mask[0];
+#endif
+        if(star) {             // ev1 / ev2: the new vertex takes its position from the far end of the edge that got it
+            C.vx[nvx].lpos = pf_pos; C.vx[nvx].rpos = pf_pos; C.vx[nvx].vtype = -1; C.vx[nvx].vw = 0; C.vx[nvx].v2v = -2;
+        } else {               // the edge that occurs once moves onto the new vertex of its partner and takes its share of the root
+            const int sp = in_side ? st_os : st_is;
+            if(sp != 0) C.ed[e].estrand = (uint8_t)sp;                       // borrow_edge_strand(e, partner)
+            if(rv >= 0) { const int k = rv >> 6; C.ed[e].mask[k] = (k == 0 ? pf_mask0 : C.ed[e].mask[k]) | (1ull << (rv & 63)); }
+            const double mweight = (in_side ? wi : wo) / total_weight * vertex_weight;
+            C.ed[e].med = pf_med + mweight; C.ed[e].mei = pf_mei + rlen;
+        }
+        if(in_side) {
+            H.ed[e].lk.inx = star ? NIL : (IDX)z;
+            if(!dupi) { H.ed[e].lk.et = (IDX)nvx; relink_out_lane(fv, e, (uint32_t)nvx); }
+        } else {
+            H.ed[e].lk.onx = (star || zfirst) ? NIL : (IDX)z;
+            if(!dupo) { H.ed[e].lk.es = (IDX)nvx; relink_in_lane(fv, e, (uint32_t)nvx); }
+        }
+    }
+    star_tail_sync();
+    // ---- lane 0: the new edge, the vertex records, the context words, what is inherently ordered
+    if(lane == 0) {
+        // a shared far list: one edge after the other, each with its endpoint written just before its walk -- the walk places an edge by the
+        // keys it meets, and the twin must still carry the old key (the root) at its old place while the first one moves, as in move_edge
+        if(dupi) { ALD_UNROLL for(int k = 0; k < 2; k++) { const int nk = (k == is) ? m : m + 1; H.ed[ge[k]].lk.et = (IDX)nk; relink_out(gfar[k], ge[k], (uint32_t)nk); } }
+        if(dupo) { ALD_UNROLL for(int k = 2; k < 4; k++) { const int nk = (k == os) ? m + 1 : m; H.ed[ge[k]].lk.es = (IDX)nk; relink_in(gfar[k], ge[k], (uint32_t)nk); } }
+        if(fh >= 0) { const IDX nx = uni(H.ed[z].lk.onx); HC.free_head = nx == NIL ? -1 : (int)nx; HC.free_cnt = uni(HC.free_cnt) - 1; }
+        else HC.slot_hw = hw + 1;
+        HC.next_id = id + 1;
+        H.ed[z].lk.es = (IDX)m; H.ed[z].lk.et = (IDX)(m + 1); H.ed[z].lk.inx = NIL; H.ed[z].lk.onx = zfirst ? (IDX)e_op : NIL;
+        H.eid[z] = (EID)id; H.hflag[z] = 0; H.ed[z].w = wz;
+        H.vx[m].in_head = (IDX)e_is; H.vx[m].out_head = zfirst ? (IDX)z : (IDX)e_op; H.vx[m].in_deg = 1; H.vx[m].out_deg = 2; H.nz[m] = 1;
+        H.vx[m + 1].in_head = (IDX)e_ip; H.vx[m + 1].out_head = (IDX)e_os; H.vx[m + 1].in_deg = 2; H.vx[m + 1].out_deg = 1; H.nz[m + 1] = 1;
+        HC.nv = m + 2; HC.maybe_broken = 1; HC.maybe_triv = 1; ev_mark_all();
+        if(inline_sp) { const double c = (abd_os < abd_is) ? abd_os : abd_is; C.ed[z].sp_off = 0; C.ed[z].sp_len = 1; C.ed[z].ecount = 1; C.ed[z].eabd = 0.0 + c; C.ed[z].s0id = id_is; C.ed[z].s0abd = c; }
+        else intersect_samples(e_is, e_os, z);
+        C.ed[z].econf = 0; C.ed[z].estrand = (uint8_t)(st_os != 0 ? st_os : st_is);      // borrow_edge_strand(z, i*) then (z, o*)
+        for(int k = 0; k < NW; k++) C.ed[z].mask[k] = (rv >= 0 && (rv >> 6) == k) ? (1ull << (rv & 63)) : 0ull;
+        C.ed[z].med = wz / total_weight * vertex_weight; C.ed[z].mei = rlen;
+#ifdef ALD_EMU_COUNT
+        { const int32_t d0 = HC.hs_dirty; HC.hs_dirty = 0; hs_insert_between(e_is, e_os, z); if(HC.hs_dirty) g_cnt_x22s[4]++; HC.hs_dirty |= d0; }
+#else
+        hs_insert_between(e_is, e_os, z);
+#endif
+        clear_vertex(root);
+    }
+    wsync();
+    return true;
+}
+#endif
+// wave-level entry (ALL lanes): the fixed form where the shape is its own, the generic form on lane 0 otherwise or when it declines.
+// A call, not inlined into the sweep (which is part of the kernel root): inlined, the root of class 0 spilled 24 VGPRs against the 18 it
+// spills without this entry, as a call 14 (class 1: 6 / 6 / 2).
+ALD_FN void decompose_vertex_extend_wave(int root, int n)
+{
+    root = uni(root); n = uni(n);
+#ifdef ALD_EMU_COUNT
+    g_cnt_x22[2]++;
+#endif
+#ifndef ALD_NO_EXTEND22
+    if(n == 3 && uni(H.vx[root].in_deg) == 2 && uni(H.vx[root].out_deg) == 2) { if(uni(extend_22(root))) return; }
+#endif
+    if(lane_id() == 0) decompose_vertex_extend(root, n);
+    wsync();
+}
 
 // ---------------------------------------------------------------- per-vertex rule evaluation (one vertex per lane)
 // scallop::classify_trivial_vertex (scallop.cc:2169-2196); -2 = needs a dominate query on need_e
@@ -3094,8 +3290,9 @@ ALD_INL bool sweep_unsplittable(int type, int degree, double max_ratio)
         { const int mm = uni(H.nz[i]);
           const bool skip = (mm & NZ_MEMO_VALID) && (((mm >> NZ_MEMO_TYPE_SHIFT) & 7) != type || ((mm & NZ_MEMO_DEG_GT1) && degree <= 1));
           if(!skip) pre = router_prepare(i); }
+        PROF_DECL;                                   // (one clock for lane 0's block and the decomposition behind it: g_dp begins where g_balance ends, as it always did)
         if(lane == 0) {
-            PROF_DECL;
+            PROF_RESET();
             // classify() comes first in the reference and build() -- with its side effect on the edge confidences -- only runs when
             // type and degree fit (router.cc:61-81, scallop.cc:1004-1030).  The six passes of one iteration classify the same vertices
             // on the same graph: the class is kept per vertex -- in the spare bits of its nonzeroset byte in LDS, wiped whenever the
@@ -3113,9 +3310,7 @@ ALD_INL bool sweep_unsplittable(int type, int degree, double max_ratio)
                 double rr = HC.ro_ratio;
                 if(rr < 0.01) {
                     trace(OP_UNSPLIT_NOW, vlog(i), type, rr);
-                    decompose_vertex_extend(i, HC.ro_npairs);
-                    PROF_ADD(PF_G_DP);
-                    act = 1;
+                    act = 1;                                 // lane 0 has decided; the decomposition itself is the whole wave's (below)
                 } else if(!(rr > ratio)) {
                     root = i; ratio = rr; best_np = HC.ro_npairs;
                     save_pairs(best_np);
@@ -3124,6 +3319,7 @@ ALD_INL bool sweep_unsplittable(int type, int degree, double max_ratio)
         }
         wsync();
         act = wread(act, 0);
+        if(act) { decompose_vertex_extend_wave(i, uni(HC.ro_npairs)); PROF_ADD(PF_G_DP); }
         if(HC.status) return true;
         if(act) { flag = true; memo_clear(); }
         cur = i + 1;
@@ -3131,14 +3327,14 @@ ALD_INL bool sweep_unsplittable(int type, int degree, double max_ratio)
     if(flag) return true;
     root = wread(root, 0);
     if(root < 0) return false;
-    if(lane == 0) {
+    best_np = wread(best_np, 0);
+    {
         PROF_DECL;
-        restore_pairs(best_np);
-        trace(OP_UNSPLIT_BEST, vlog(root), type, ratio);
-        decompose_vertex_extend(root, best_np);
+        if(lane == 0) { restore_pairs(best_np); trace(OP_UNSPLIT_BEST, vlog(root), type, ratio); }
+        wsync();
+        decompose_vertex_extend_wave(root, best_np);
         PROF_ADD(PF_G_DP);
     }
-    wsync();
     return true;
 }
 
