@@ -19,6 +19,8 @@ import numpy as np
 
 import aletsch_amd as A
 from aletsch_amd.packed import PackedGraphs
+import common
+import device_run as DR
 import shapes
 
 MIN_EVENTS = 10
@@ -537,9 +539,8 @@ def star_form_lines(src):
 def oracle_of(ps, without=()):
     key = ("oracle", ps, tuple(sorted(without)))
     if key not in _CACHE:
-        import common
         labels, pg, graphs, prm = site_batches(without)[ps]
-        _CACHE[key] = common.oracle_assert_sites(pg, threads=max(1, min(16, len(os.sched_getaffinity(0)))), params=prm)
+        _CACHE[key] = common.oracle_assert_sites(pg, threads=DR.THREADS, params=prm)
     return _CACHE[key]
 
 
@@ -547,7 +548,6 @@ def raw_results():
     """the raw cases through the oracle's pre-steps and the raw build of the emulation -> (oracle status per item, site names, emulation status, lines)"""
     if "raw" not in _CACHE:
         import ctypes as C
-        import common
         O = common.oracle_lib()
         O.ora_pre_assemble.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_void_p)]
         O.ora_staged_view.argtypes = [C.c_void_p, C.c_void_p]; O.ora_staged_free.argtypes = [C.c_void_p]; O.ora_staged_boundary_maps.argtypes = [C.c_void_p] * 5
@@ -628,7 +628,6 @@ def census(without=()):
     and without it (the collect phase publishes a whole round of finished edges at once when nothing is traced) -- plus the raw cases"""
     key = ("census", tuple(sorted(without)))
     if key not in _CACHE:
-        import common
         c = Census()
         for ps, (labels, pg, graphs, prm) in site_batches(without).items():
             want, traces, sites = oracle_of(ps, without)
@@ -662,7 +661,6 @@ def successor_batch(per_pair=PER_PAIR):
     default set ends differently under them): per exit group per_pair x 6 failing graphs drawn across the group's families, the witness kinds in turn"""
     key = ("successor", per_pair)
     if key not in _CACHE:
-        import common
         cases = [(l, g) for l, ps, g in all_cases() if ps in ("default", "wide")]
         wit = {k: [g for kk, g in witnesses(repeat=6) if kk == k] for k in WITNESS_KINDS}
         graphs = []; labels = []; kinds = []
@@ -674,7 +672,7 @@ def successor_batch(per_pair=PER_PAIR):
                 l, g = pool[(i * step) % len(pool)]; k = WITNESS_KINDS[i % len(WITNESS_KINDS)]
                 graphs += [g, wit[k][(i // len(WITNESS_KINDS)) % len(wit[k])]]; labels += [l, "witness " + k]; kinds += [group, k]
         pg = pack(graphs); prm = params(**PARAM_SETS["wide"])
-        want, traces, sites = common.oracle_assert_sites(pg, threads=max(1, min(16, len(os.sched_getaffinity(0)))), params=prm)
+        want, traces, sites = common.oracle_assert_sites(pg, threads=DR.THREADS, params=prm)
         _CACHE[key] = dict(pg=pg, params=prm, graphs=graphs, labels=labels, kinds=kinds, want=want, traces=traces, sites=sites)
     return _CACHE[key]
 
@@ -698,59 +696,20 @@ TRACE_CAP = 256                           # the longest op trace is that of a 70
 SLAB_CLASS_GRAPHS = 80                    # graphs per batch in the classes whose state lives in a slab of 13 MB and more per wave (what the class matrix runs there)
 
 
-def run_on_device(pg, prm=None, first=0, twin="0", raw=False, env=None):
-    """the batch through the library the process has loaded, every graph traced -> (DecompResult, class -> (graphs, waves of the last run), traces)"""
-    env = dict(env or {}, ALD_DEBUG_FIRST_CLASS=str(first), ALD_DEBUG_TWIN=twin)
-    old = {k: os.environ.get(k) for k in env}                 # what the caller had set is put back, not dropped
-    os.environ.update(env)
-    try:
-        with A.DecompBatch(0, prm, trace_events=TRACE_CAP) as b:
-            if raw: b.add_packed_raw(pg, 10000)
-            else: b.add(pg)
-            b.upload(); b.run(); b.download()
-            info = {c: b.class_info(c) for c in range(14)}
-            used = {c: (i["n_graphs"], i["blocks_last_run"]) for c, i in info.items() if i["n_graphs"]}
-            return b.result(), used, [[(c, a, bb, v) for c, a, bb, v in b.trace(g)] for g in range(pg.n)]
-    finally:
-        for k, v in old.items():
-            if v is None: os.environ.pop(k, None)
-            else: os.environ[k] = v
-
-
-def device_mismatches(tag, got, traces, want, want_traces):
-    """differences between a device run and the oracle: statuses, no path from a failed graph, records (conf within 1e-9 as in the whole GPU tier,
-    everything else bit for bit) and the WHOLE op trace of every graph -- it must end where the oracle's ends"""
-    import common
-    n = len(want_traces); bad = []
-    if not np.array_equal(got.status, want.status):
-        g = int(np.nonzero(got.status != want.status)[0][0]); return [(tag, "status of graph %d" % g, int(want.status[g]), int(got.status[g]))]
-    bad += [(tag,) + tuple(x) for x in common.compare_results(want, got, n, conf_tol=1e-9)]
-    if (np.diff(got.path_offset)[want.status >= 100] != 0).any(): bad.append((tag, "a failed graph published a path"))
-    for g in range(n):
-        assert len(want_traces[g]) < TRACE_CAP
-        if traces[g] != want_traces[g]:
-            bad.append((tag, "trace of graph %d" % g, next((i for i, (x, y) in enumerate(zip(traces[g], want_traces[g])) if x != y), min(len(traces[g]), len(want_traces[g]))))); break
-    return bad
-
-
-def select_results(res, idx):
-    import common
-    return common.select_results(res, idx)
-
-
 def site_mismatches_on_device(first, twin, cls=None):
     """every site batch with the first class forced -> (graphs run, mismatches); cls: the class the small graphs must end in (None: not checked).
     The classes whose state lives in the slab take an even-stride sample of SLAB_CLASS_GRAPHS graphs per parameter set"""
     tot = 0; bad = []
     for ps, (labels, pg, graphs, prm) in site_batches().items():
         want, traces, sites = oracle_of(ps)
+        assert max(len(t) for t in traces) < TRACE_CAP
         idx = np.arange(pg.n)
         if cls is not None and cls >= 10: idx = idx[::max(1, -(-pg.n // SLAB_CLASS_GRAPHS))]
-        sub = pg.select(idx) if len(idx) < pg.n else pg
-        got, used, mine = run_on_device(sub, prm, first, twin)
+        r = DR.run(pg.select(idx) if len(idx) < pg.n else pg, prm, first=first, twin=twin, trace_cap=TRACE_CAP)
         tag = "%s, first class %d, twin %s" % (ps, first, twin)
-        if cls is not None and not (cls in used and min(used) >= cls): bad.append((tag, "classes", used))
-        bad += device_mismatches(tag, got, mine, select_results(want, idx), [traces[int(g)] for g in idx])
+        if cls is not None and cls not in r.classes: bad.append((tag, "classes", r.classes))
+        bad += DR.oracle_mismatches(tag, r, common.select_results(want, idx), None, traces, traced=idx,
+                                    want_classes=None if cls is None else set(range(cls, DR.N_CLASSES)))
         tot += len(idx)
     return tot, bad
 
@@ -762,7 +721,6 @@ def raw_star_and_late_items(stride=4):
     out only when the ORACLE's pre-steps assert on it; the caller asserts how many."""
     if "rawform" not in _CACHE:
         import ctypes as C
-        import common
         O = common.oracle_lib()
         O.ora_pre_assemble.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_void_p)]
         O.ora_staged_view.argtypes = [C.c_void_p, C.c_void_p]; O.ora_staged_free.argtypes = [C.c_void_p]; O.ora_staged_boundary_maps.argtypes = [C.c_void_p] * 5
@@ -795,7 +753,6 @@ GROWN_MAX_EXONS = 38                      # the hubs have 37 vertices and grow t
 def extra_successor_batch(which, per_pair=16):
     key = ("successor2", which, per_pair)
     if key not in _CACHE:
-        import common
         rng = np.random.default_rng(6111 if which == "grown" else 6112)
         wit = {k: [g for kk, g in witnesses(repeat=6) if kk == k] for k in WITNESS_KINDS}
         group = "grown past max_num_exons" if which == "grown" else "capacity climb"
@@ -806,6 +763,6 @@ def extra_successor_batch(which, per_pair=16):
             k = WITNESS_KINDS[i % len(WITNESS_KINDS)]
             graphs += [g, wit[k][(i // len(WITNESS_KINDS)) % len(wit[k])]]; labels += [group, "witness " + k]; kinds += [group, k]
         pg = pack(graphs); prm = params(r0=0.0, max_exons=GROWN_MAX_EXONS) if which == "grown" else params(**PARAM_SETS["wide"])
-        want, st, _, traces = common.oracle_run(pg, threads=max(1, min(16, len(os.sched_getaffinity(0)))), trace=True, params=prm)
+        want, st, _, traces = common.oracle_run(pg, threads=DR.THREADS, trace=True, params=prm)
         _CACHE[key] = dict(pg=pg, params=prm, graphs=graphs, labels=labels, kinds=kinds, want=want, traces=traces, stats=st, group=group)
     return _CACHE[key]

@@ -17,13 +17,13 @@ oracle's bit for bit mean the same sequence of graph states, so the oracle's cen
 from __future__ import annotations
 
 import ctypes as C
-import os
 
 import numpy as np
 
 import aletsch_amd as A
 from aletsch_amd.packed import PackedGraphs
 import common
+from device_run import THREADS
 import shapes
 
 CLASSES = tuple(range(11)) + (13,)          # what pick_class chooses from (the twins 11 / 12 are a placement choice of the GPU host)
@@ -32,7 +32,6 @@ TRACE_STRIDE = 4                            # the op trace is compared on every 
 TRACE_CAP = 1 << 13
 FANS = (1, 2, 3, 4, 5, 8, 16)
 ROUTERS = ((2, 2), (2, 3), (3, 3), (4, 4), (6, 6))
-THREADS = max(1, min(16, len(os.sched_getaffinity(0))))
 _CACHE = {}
 
 

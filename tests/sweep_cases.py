@@ -29,6 +29,7 @@ import aletsch_amd as A
 from aletsch_amd.packed import PackedGraphs, export_via
 import class_cases as CC
 import common
+import device_run as DR
 import shapes
 
 MIN_EVENTS = 10
@@ -307,38 +308,16 @@ def expected_classes(name: str, first: int):
     return np.maximum(natural_classes(name), first)
 
 
-HUGE_BATCH = 32                              # class 13: ~105 MB of slab per wave, so no batch of it holds more than 32 graphs
-
-
 def device_mismatches(name: str, first: int = 0, cls: int = 0):
-    """run `name` through the library the process has loaded (the caller has set ALD_DEBUG_FIRST_CLASS = first and ALD_DEBUG_TWIN; cls: the
-    class that stands for `first`, its twin or itself) against the oracle -> list of differences: the classes the graphs ran in, statuses,
-    records (conf within 1e-9 as in the whole GPU tier, everything else bit for bit) and, for every graph that does not end on an invariant
-    status, the iteration count and the whole op trace"""
-    from test_pre_steps_cpu import common_select_results
+    """run `name` through the library the process has loaded with the first class forced (cls: the class that stands for `first`, its twin or
+    itself) -> device_run.oracle_mismatches per batch: the classes the graphs ran in, statuses, records and, for every graph that does not
+    end on an invariant status, the iteration count and the whole op trace"""
     o = runs()[name]; pg = o["pg"]; bad = []
     want_cls = expected_classes(name, first).copy(); want_cls[want_cls == first] = cls
-    step = HUGE_BATCH if cls == 13 else pg.n
-    for a in range(0, pg.n, step):
-        idx = np.arange(a, min(a + step, pg.n)); sub = pg if len(idx) == pg.n else pg.select(idx)
-        with A.DecompBatch(0, o["params"], trace_events=TRACE_CAP) as b:
-            b.add(sub); b.upload(); b.run(); b.download()
-            got = b.result(); it = b.iterations()
-            used = {c: b.class_info(c)["n_graphs"] for c in range(14)}; used = {c: k for c, k in used.items() if k}
-            traces = [[(c, x, y, v) for c, x, y, v in b.trace(k)] for k in range(len(idx))]
-        exp = {int(c): int((want_cls[idx] == c).sum()) for c in np.unique(want_cls[idx])}
-        if used != exp: bad.append((name, "classes", used, exp))
-        want = common_select_results(o["res"], idx)
-        if not np.array_equal(got.status, want.status): bad.append((name, "status", int(a)))
-        bad += [(name, int(a)) + tuple(x) for x in common.compare_results(want, got, len(idx), conf_tol=1e-9)]
-        good = want.status < 100
-        if not np.array_equal(it[good], o["iters"][idx][good]): bad.append((name, "iterations", (idx[good][it[good] != o["iters"][idx][good]])[:5].tolist()))
-        for k in np.nonzero(good)[0]:
-            mine, ref = traces[k], o["traces"][int(idx[k])]
-            if mine != ref:
-                at = next((i for i, (x, y) in enumerate(zip(mine, ref)) if x != y), min(len(mine), len(ref)))
-                bad.append((name, "trace of graph %d (%s)" % (idx[k], o["labels"][int(idx[k])] if o["labels"] else ""), "first divergence at %d" % at,
-                            mine[at] if at < len(mine) else None, ref[at] if at < len(ref) else None))
+    for idx in DR.in_chunks(pg.n, cls):
+        r = DR.run(pg if len(idx) == pg.n else pg.select(idx), o["params"], first=first, twin="1" if cls in DR.TWIN_OF else "0", trace_cap=TRACE_CAP)
+        bad += DR.oracle_mismatches("%s from graph %d" % (name, idx[0]), r, common.select_results(o["res"], idx), o["iters"][idx], o["traces"],
+                                    want_classes=DR.class_counts(want_cls[idx]), traced=idx, skip_failed=True)
     return bad
 
 

@@ -17,11 +17,11 @@ import pytest
 import aletsch_amd as A
 import assert_cases as AC
 import common
+import device_run as DR
 import shapes
 
 MIN_EVENTS = AC.MIN_EVENTS
 K = AC.K
-THREADS = max(1, min(16, len(os.sched_getaffinity(0))))
 BUILDS = {"lists": dict(), "rows": dict(rows=True), "keep": dict(keep=True)}
 
 
@@ -48,7 +48,7 @@ def test_emulation_matches_oracle_on_every_failing_graph(build):
         assert (np.diff(got.path_offset)[failed] == 0).all(), (ps, build)
         assert ((ln != 0) == (got.status != 0)).all(), (ps, build)              # every status has the line that raised it, and only those
         for g in range(pg.n):
-            assert mine[g] == traces[g], f"{ps}, {build}, graph {g} ({labels[g]}): first divergence at {next((i for i, (a, b) in enumerate(zip(mine[g], traces[g])) if a != b), min(len(mine[g]), len(traces[g])))} of {len(traces[g])}"
+            assert mine[g] == traces[g], f"{ps}, {build}, graph {g} ({labels[g]}): first divergence at {DR.first_divergence(mine[g], traces[g])} of {len(traces[g])}"
         n += pg.n
     print(f"\n{build}: {n} graphs that end on an assert, 0 mismatches")
 
@@ -113,7 +113,7 @@ def test_witnesses_need_what_they_claim():
     """(a) grows past its own V, (b) holds more live edges than it was staged with, (c) phasing lists, (d) several samples on an edge,
     (e) at most 6 vertices, (f) two router builds or more in a sweep that ends on `best`: from the oracle's statistics and trace"""
     w = AC.witnesses(); pg = AC.pack([g for _, g in w]); prm = AC.params(**AC.PARAM_SETS["wide"])
-    want, st, _, tr = common.oracle_run(pg, threads=THREADS, trace=True, params=prm)
+    want, st, _, tr = common.oracle_run(pg, threads=DR.THREADS, trace=True, params=prm)
     assert (want.status == 0).all()
     for j, (kind, g) in enumerate(w):
         V, E = g["V"], len(g["edges"])

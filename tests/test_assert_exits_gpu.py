@@ -24,13 +24,14 @@ import pytest
 import assert_cases as AC
 import class_cases as CC
 import common
+import device_run as DR
 
 pytestmark = pytest.mark.gpu
 
-KERNELS = [(c, "0", c) for c in CC.CLASSES] + [(7, "1", 11), (8, "1", 12)]
+KERNELS, IDS = DR.forced_kernels(CC.CLASSES, twins=(11, 12))
 
 
-@pytest.mark.parametrize("first,twin,cls", KERNELS, ids=["class%d" % k[2] for k in KERNELS])
+@pytest.mark.parametrize("first,twin,cls", KERNELS, ids=IDS)
 def test_failing_graphs_in_every_plain_kernel(first, twin, cls):
     n, bad = AC.site_mismatches_on_device(first, twin, cls)
     assert not bad, bad[:3]
@@ -53,21 +54,22 @@ def test_star_and_late_exit_cases_in_raw_form():
     assert dropped == 0, dropped                                                  # the oracle's pre-steps take every one of them
     assert {int(v) - 3 for v in raw_pg.g_nv} >= set(AC.STAR_FANS)                 # every fan size is there (a star of k has k + 3 vertices)
     want, traces, sites = common.oracle_assert_sites(staged, threads=CC.THREADS)
+    assert max(len(t) for t in traces) < AC.TRACE_CAP
     assert (want.status >= 100).sum() >= 0.9 * staged.n and len(set(labels)) >= 8
     for first in (0, 1, 2):
-        got, used, mine = AC.run_on_device(raw_pg, None, first, raw=True)
-        bad = AC.device_mismatches("raw, first class %d" % first, got, mine, want, traces)
+        r = DR.run(raw_pg, first=first, raw=True, trace_cap=AC.TRACE_CAP)
+        bad = DR.oracle_mismatches("raw, first class %d" % first, r, want, None, traces, want_classes=set(range(first, DR.N_CLASSES)))
         assert not bad, bad[:3]
-        assert min(used) >= first, used
 
 
 def test_three_orders_of_the_interleaved_batch():
     """(see the module text: statistical).  The batch is sized from the grid the diagnostics report."""
     env = {"ALD_WG_PER_CU": "1"}
     o = AC.successor_batch(); pg0 = o["pg"]; prm = o["params"]
-    _, used, _ = AC.run_on_device(pg0, prm, AC.SUCCESSOR_CLASS, env=env)
-    assert set(used) == {AC.SUCCESSOR_CLASS}, used                               # one class, one work list
-    waves = used[AC.SUCCESSOR_CLASS][1]                                           # = the CUs of this device once the batch is large enough
+    assert max(len(t) for t in o["traces"]) < AC.TRACE_CAP
+    sized = DR.run(pg0, prm, first=AC.SUCCESSOR_CLASS, trace_cap=AC.TRACE_CAP, env=env)
+    assert set(sized.classes) == {AC.SUCCESSOR_CLASS}, sized.classes             # one class, one work list
+    waves = sized.waves[AC.SUCCESSOR_CLASS]                                       # = the CUs of this device once the batch is large enough
     copies = -(-8 * max(waves, 64) // pg0.n) + 1
     o, idx = AC.order_batch(copies)
     rng = np.random.default_rng(6109)
@@ -75,13 +77,13 @@ def test_three_orders_of_the_interleaved_batch():
     runs = {}
     for name, order in orders.items():
         g_of = idx[order]                                                        # position in this run -> graph of the interleaved batch
-        got, used, mine = AC.run_on_device(pg0.select(g_of), prm, AC.SUCCESSOR_CLASS, env=env)
-        n_graphs, n_waves = used[AC.SUCCESSOR_CLASS]
-        assert set(used) == {AC.SUCCESSOR_CLASS} and n_graphs >= 8 * n_waves, (name, used)
-        bad = AC.device_mismatches(name, got, mine, AC.select_results(o["want"], g_of), [o["traces"][int(g)] for g in g_of])
+        r = DR.run(pg0.select(g_of), prm, first=AC.SUCCESSOR_CLASS, trace_cap=AC.TRACE_CAP, env=env)
+        n_waves = r.waves[AC.SUCCESSOR_CLASS]
+        assert set(r.classes) == {AC.SUCCESSOR_CLASS} and r.classes[AC.SUCCESSOR_CLASS] >= 8 * n_waves, (name, r.classes, r.waves)
+        bad = DR.oracle_mismatches(name, r, common.select_results(o["want"], g_of), None, o["traces"], traced=g_of)
         assert not bad, bad[:3]
         back = np.argsort(order, kind="stable")                                   # this run's results in the given order
-        runs[name] = (AC.select_results(got, back), [mine[int(k)] for k in back])
+        runs[name] = (common.select_results(r.result, back), [r.traces[int(k)] for k in back])
     ref, ref_tr = runs["given"]
     for name in ("reversed", "permuted"):
         res, tr = runs[name]

@@ -11,8 +11,8 @@ import pytest
 
 import class_cases as CC
 import common
+import device_run as DR
 import shapes
-from test_pre_steps_cpu import common_select_results
 
 
 def test_census_of_the_mix():
@@ -43,7 +43,7 @@ def test_forced_hubs_fill_the_group_of_classes_10_and_13():
 def _check_traces(o, mine, idx, what):
     for k, g in enumerate(idx):
         a, b = mine[k], o["traces"][int(g)]
-        assert a == b, f"{what}, graph {int(g)}: first divergence at {next((i for i, (x, y) in enumerate(zip(a, b)) if x != y), min(len(a), len(b)))}"
+        assert a == b, f"{what}, graph {int(g)}: first divergence at {DR.first_divergence(a, b)}"
 
 
 @pytest.mark.parametrize("part", ["staged", "second"])
@@ -87,7 +87,7 @@ def test_raw_class_matches_oracle(cls, part):
     assert np.array_equal(cl, CC.expected_classes(part, cls)), (cls, np.unique(cl))
     assert (got.status[~ok] >= 100).all(), (cls, got.status[~ok])
     keep = np.nonzero(ok)[0]
-    bad = common.compare_results(o["res"], common_select_results(got, keep), len(keep))
+    bad = common.compare_results(o["res"], common.select_results(got, keep), len(keep))
     assert not bad, (cls, part, bad[:3])
     good = o["res"].status == 0
     assert np.array_equal(it[keep][good], o["iters"][good]), (cls, part)

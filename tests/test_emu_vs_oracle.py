@@ -6,6 +6,7 @@ import pytest
 
 import aletsch_amd as A
 import common
+import device_run as DR
 
 
 @pytest.mark.parametrize("name", list(common.PARITY_CONFIGS))
@@ -89,7 +90,7 @@ def test_engine_op_trace_matches_oracle():
         codes = np.zeros(3 * max(1, n.value), np.int32); vals = np.zeros(max(1, n.value))
         E.emu_result_trace(h, g, C.byref(n), codes.ctypes.data_as(C.POINTER(C.c_int32)), vals.ctypes.data_as(C.POINTER(C.c_double)), n.value)
         mine = [(int(codes[3 * i]), int(codes[3 * i + 1]), int(codes[3 * i + 2]), float(vals[i])) for i in range(n.value)]
-        assert mine == traces[g], f"graph {g}: first divergence at {next((i for i, (a, b) in enumerate(zip(mine, traces[g])) if a != b), min(len(mine), len(traces[g])))}"
+        assert mine == traces[g], f"graph {g}: first divergence at {DR.first_divergence(mine, traces[g])}"
     E.emu_result_free(h)
 
 

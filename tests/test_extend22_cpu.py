@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 
 import common
+import device_run as DR
 import extend22_cases as X
 
 ROOT = common.ROOT
@@ -26,7 +27,7 @@ def _check(name, want, st, traces, got, it, tr, what):
     assert not bad, f"{name}, {what}: {len(bad)} mismatches, first {bad[:3]}"
     assert np.array_equal(it, st[:, 3]), (name, what, np.nonzero(it != st[:, 3])[0][:10])
     for g in range(len(traces)):
-        assert tr[g] == traces[g], f"{name}, {what}, graph {g}: first divergence at {next((i for i, (a, b) in enumerate(zip(tr[g], traces[g])) if a != b), min(len(tr[g]), len(traces[g])))}"
+        assert tr[g] == traces[g], f"{name}, {what}, graph {g}: first divergence at {DR.first_divergence(tr[g], traces[g])}"
 
 
 @pytest.mark.parametrize("name", CASES)

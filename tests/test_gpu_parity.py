@@ -8,6 +8,7 @@ import pytest
 
 import aletsch_amd as A
 import common
+import device_run as DR
 
 pytestmark = pytest.mark.gpu
 
@@ -24,21 +25,14 @@ def test_hip_matches_oracle(name):
 
 def test_iteration_counts_match_oracle():
     pg = A.synth(**common.PARITY_CONFIGS["cfg2_64v256e"])
-    _, st, _, _ = common.oracle_run(pg)
-    with A.DecompBatch(0) as b:
-        b.add(pg); b.upload(); b.run(); b.download()
-        it = b.iterations()
-    assert np.array_equal(it, st[:, 3])
+    want, st, _, _ = common.oracle_run(pg)
+    assert not DR.oracle_mismatches("cfg2_64v256e", DR.run(pg), want, st[:, 3])
 
 
 def test_op_trace_matches_oracle_on_gpu():
     pg = A.synth(**dict(common.PARITY_CONFIGS["everything"], n_graphs=40))
-    _, _, _, traces = common.oracle_run(pg, trace=True)
-    with A.DecompBatch(0, trace_events=4096) as b:
-        b.add(pg); b.upload(); b.run(); b.download()
-        for g in range(pg.n):
-            mine = [(c, a, bb, v) for c, a, bb, v in b.trace(g)]
-            assert mine == traces[g], f"graph {g} diverges from the oracle's op trace"
+    want, st, _, traces = common.oracle_run(pg, trace=True)
+    assert not DR.oracle_mismatches("everything", DR.run(pg, trace_cap=4096), want, st[:, 3], traces)
 
 
 def test_nondefault_parameters_on_gpu():
@@ -124,8 +118,7 @@ def test_full_size_properties():
     assert np.array_equal(sub.path_vertices, r1.path_vertices[: int(r1.pv_offset[lim])])
     # oracle parity on the WHOLE full-size batch (the oracle runs on all host cores: ~10 s); rare interleavings of the rule cascade
     # only show up at this scale (a stale evaluation that changed 7 graphs in 100 000 was caught exactly here)
-    import os
-    want = common.oracle_run(pg, threads=max(1, min(16, len(os.sched_getaffinity(0)))))[0]
+    want = common.oracle_run(pg, threads=DR.THREADS)[0]
     assert not common.compare_results(want, r1, n, conf_tol=1e-9)
 
 
@@ -375,12 +368,7 @@ def test_slab_twins_of_the_large_lds_classes(monkeypatch):
     want = common.oracle_run(pg, threads=8)[0]
     for force in ("1", "0"):
         monkeypatch.setenv("ALD_DEBUG_TWIN", force)
-        with A.DecompBatch(0) as b:
-            b.add(pg); b.upload(); b.run(); b.download()
-            got = b.result()
-            used = {c: b.class_info(c)["n_graphs"] for c in range(14) if b.class_info(c)["n_graphs"]}
-        assert not common.compare_results(want, got, pg.n, conf_tol=1e-9), force
-        assert (set(used) <= {11, 12, 9}) if force == "1" else (set(used) <= {7, 8, 9}), (force, used)
+        assert not DR.oracle_mismatches("twins " + force, DR.run(pg), want, want_classes={11, 12, 9} if force == "1" else {7, 8, 9})
     monkeypatch.setenv("ALD_DEBUG_TWIN", "1"); monkeypatch.setenv("ALD_DEBUG_UNDERCLASS", "1")
     small = pg.select(np.arange(12))
     with A.DecompBatch(0) as b:                               # started one class too low: overflow -> the next twin / class 9
@@ -390,22 +378,14 @@ def test_slab_twins_of_the_large_lds_classes(monkeypatch):
     assert not common.compare_results(w2, got, small.n, conf_tol=1e-9)
 
 
-def _host_threads():
-    import os
-    return max(1, min(16, len(os.sched_getaffinity(0))))
-
-
 def test_cfg3_mixed_batch_at_spec():
     """BASELINE.json configs[2] at spec: 10 000 graphs, V ~ U{8..512}, E = 4V (seed 1003) -- the one place where nine
     size classes, three side streams and the LDS / slab-twin choice run together -- compared with the oracle graph by graph"""
     pg = A.synth(seed=1003, n_graphs=10000, v_min=8, v_max=512, edges_per_vertex=4)
-    want = common.oracle_run(pg, threads=_host_threads())[0]
-    with A.DecompBatch(0) as b:
-        b.add(pg); b.upload(); b.run(); b.download()
-        got = b.result()
-        used = {c: b.class_info(c)["n_graphs"] for c in range(14) if b.class_info(c)["n_graphs"]}
-    assert not common.compare_results(want, got, pg.n, conf_tol=1e-9)
-    assert (got.status == 0).all() and len(used) >= 8, used
+    want = common.oracle_run(pg, threads=DR.THREADS)[0]
+    r = DR.run(pg)
+    assert not DR.oracle_mismatches("cfg3", r, want)
+    assert (r.result.status == 0).all() and len(r.classes) >= 8, r.classes
 
 
 def test_flow_weights_at_full_size():
@@ -414,14 +394,11 @@ def test_flow_weights_at_full_size():
     retried one class up"""
     n = 100000
     pg = A.synth(seed=1002, n_graphs=n, v_min=64, v_max=64, fixed_edges=256, weight_mode=2)
-    want = common.oracle_run(pg, threads=_host_threads())[0]
-    with A.DecompBatch(0) as b:
-        b.add(pg); b.upload(); b.run(); b.download()
-        got = b.result()
-        classes = {c: b.class_info(c)["n_graphs"] for c in range(14) if b.class_info(c)["n_graphs"]}
-    assert not common.compare_results(want, got, n, conf_tol=1e-9)
-    assert (got.status == 0).all()
-    assert set(classes) - {1}, f"expected at least one capacity retry out of class 1: {classes}"
+    want = common.oracle_run(pg, threads=DR.THREADS)[0]
+    r = DR.run(pg)
+    assert not DR.oracle_mismatches("flow weights", r, want)
+    assert (r.result.status == 0).all()
+    assert set(r.classes) - {1}, f"expected at least one capacity retry out of class 1: {r.classes}"
 
 
 def test_fuzz_slice():
@@ -430,7 +407,7 @@ def test_fuzz_slice():
     coverage threshold and max_num_exons, explicit edge counts, permuted creation ranks"""
     import time
     rng = np.random.default_rng(20260)
-    thr = _host_threads()
+    thr = DR.THREADS
     t_end = time.time() + 60.0; ntot = 0; k = 0
     while time.time() < t_end:
         k += 1
@@ -472,7 +449,7 @@ def test_edge_creation_rank_on_gpu():
     for e in pg.g_ne:
         r[o:o + e] = rng.permutation(int(e)); o += int(e)
     perm.edge_rank = r
-    want = common.oracle_run(perm, threads=_host_threads())[0]
+    want = common.oracle_run(perm, threads=DR.THREADS)[0]
     got = A.decompose(perm, 0)
     assert not common.compare_results(want, got, pg.n, conf_tol=1e-9)
     assert common.compare_results(base, got, pg.n), "a permuted creation rank should change some decomposition"
@@ -622,8 +599,7 @@ def test_raw_graphs_through_the_pre_steps_on_gpu():
     assert (got.status[asserted] >= 100).all()
     batch = PackedGraphs.concat(want_parts)
     want = common.oracle_run(batch, threads=4)[0]
-    import test_pre_steps_cpu as T
-    sub = T.common_select_results(got, np.nonzero(~asserted)[0])
+    sub = common.select_results(got, np.nonzero(~asserted)[0])
     assert not common.compare_results(want, sub, batch.n, conf_tol=1e-9)
     assert (want.status == 0).sum() > 200
     # the bulk form stages the same batch
@@ -794,11 +770,10 @@ def test_cfg4_rank0_shard_at_spec():
     """BASELINE configs[3] as one rank sees it: rank 0's shard of the 1 M-graph job, 125 000 x 64v/256e, seed 1004 + rank,
     against the oracle on all host cores.  (The other seven ranks run the same code on seeds 1005..1011; the merge of two such shards
     in rank order is tests/test_distributed_cpu.py::test_cfg4_shards_merge_in_rank_order.)"""
-    import os
     pg = A.synth(seed=1004, n_graphs=125000, v_min=64, v_max=64, fixed_edges=256)
     got = A.decompose(pg, device=0)
     assert int((got.status != 0).sum()) == 0
-    want = common.oracle_run(pg, threads=max(1, len(os.sched_getaffinity(0))))[0]
+    want = common.oracle_run(pg, threads=DR.THREADS)[0]
     assert not common.compare_results(want, got, pg.n, conf_tol=1e-9)
 
 

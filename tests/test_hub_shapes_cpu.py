@@ -8,24 +8,23 @@ the kernel headers --, and runs the batch through the single-lane emulation (lis
 records, iteration counts and the op trace.  tests/test_hub_shapes_gpu.py repeats the comparison on the device, where the wave-parallel forms
 (star_reg, router_prepare) exist."""
 import ctypes as C
-import os
 
 import numpy as np
 import pytest
 
 import common
+import device_run as DR
 import shapes
 
 MIN_EVENTS = 10
 K = shapes.kernel_constants()
-THREADS = max(1, min(16, len(os.sched_getaffinity(0))))
 
 
 def _oracle(pg, params=None):
     if not hasattr(_oracle, "memo"):
         _oracle.memo = {}
     if id(pg) not in _oracle.memo:
-        _oracle.memo[id(pg)] = shapes.census_of(pg, threads=THREADS, params=params)
+        _oracle.memo[id(pg)] = shapes.census_of(pg, threads=DR.THREADS, params=params)
     return _oracle.memo[id(pg)]
 
 
@@ -104,10 +103,10 @@ def test_emulation_matches_oracle_on_the_hub_batch(build):
         assert not bad, (name, bad[:3])
         assert (want.status == 0).all(), (name, np.nonzero(want.status)[0][:10])
         assert np.array_equal(it, st[:, 3]), name
-        traces = common.oracle_run(pg, threads=THREADS, trace=True, params=prm)[3]
+        traces = common.oracle_run(pg, threads=DR.THREADS, trace=True, params=prm)[3]
         mine = emu_traces(pg, params=prm, **kw)
         for g in range(pg.n):
-            assert mine[g] == traces[g], f"{name}, graph {g}: first divergence at {next((i for i, (a, b) in enumerate(zip(mine[g], traces[g])) if a != b), min(len(mine[g]), len(traces[g])))}"
+            assert mine[g] == traces[g], f"{name}, graph {g}: first divergence at {DR.first_divergence(mine[g], traces[g])}"
 
 
 def test_hub_batch_started_one_class_too_low(monkeypatch):
@@ -131,7 +130,7 @@ def test_hubs_with_a_zero_count_edge_end_as_the_oracle_does():
     pg, _ = shapes.zero_count_batch()
     want, st, per_graph = _oracle(pg)
     assert (want.status >= 100).all()
-    traces = common.oracle_run(pg, threads=THREADS, trace=True)[3]
+    traces = common.oracle_run(pg, threads=DR.THREADS, trace=True)[3]
     fired = sum(1 for t in traces if any(ev[0] in (7, 8) for ev in t))                # OP_UNSPLIT_NOW / OP_UNSPLIT_BEST
     assert fired >= MIN_EVENTS, fired
     for kw in (dict(), dict(rows=True), dict(keep=True)):
@@ -146,7 +145,7 @@ def test_census_notices_a_missing_generator():
     """the batch without its hubs of STAR_MAX + 1 edges leaves that bucket short: the census condition is not met by the other graphs' leftovers"""
     S = K["STAR_MAX"] + 1
     pg, _ = shapes.hub_batch(without=(S,))
-    _, _, per_graph = shapes.census_of(pg, threads=THREADS)
+    _, _, per_graph = shapes.census_of(pg, threads=DR.THREADS)
     _, _, cl = common.emu_run(pg)
     req = shapes.Census(per_graph, cl, pg.g_nv, K).required()
     assert min(req["fan %d in" % S], req["fan %d out" % S]) < MIN_EVENTS, (req["fan %d in" % S], req["fan %d out" % S])
@@ -155,7 +154,6 @@ def test_census_notices_a_missing_generator():
 def test_raw_hub_graphs_through_the_pre_steps():
     """hub graphs handed over raw (phases as exon-coordinate lists): the load phase folds the boundary edges at the source and the sink,
     which is where hubs live; against the oracle's pre-steps + decomposition"""
-    import test_pre_steps_cpu as T
     from aletsch_amd.packed import PackedGraphs
     O = common.oracle_lib()
     O.ora_pre_assemble.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_void_p)]
@@ -164,8 +162,8 @@ def test_raw_hub_graphs_through_the_pre_steps():
     got, _ = common.emu_run_raw(items)
     ok = np.array(ok)
     assert ok.sum() >= 0.9 * len(ok)
-    want = common.oracle_run(PackedGraphs.concat(staged), threads=THREADS)[0]
-    assert not common.compare_results(want, T.common_select_results(got, np.nonzero(ok)[0]), len(staged), conf_tol=1e-9)
+    want = common.oracle_run(PackedGraphs.concat(staged), threads=DR.THREADS)[0]
+    assert not common.compare_results(want, common.select_results(got, np.nonzero(ok)[0]), len(staged), conf_tol=1e-9)
     assert (got.status[~ok] >= 100).all()
 
 

@@ -12,19 +12,19 @@ import pytest
 
 import aletsch_amd as A
 import common
+import device_run as DR
 import shapes
 from test_batch_features_gpu import assert_tables_equal, host_table
 
 pytestmark = pytest.mark.gpu
 
 K = shapes.kernel_constants()
-THREADS = max(1, min(16, len(os.sched_getaffinity(0))))
 _MEMO = {}
 
 
 def oracle(pg, params=None):
     if id(pg) not in _MEMO:
-        _MEMO[id(pg)] = shapes.census_of(pg, threads=THREADS, params=params)
+        _MEMO[id(pg)] = shapes.census_of(pg, threads=DR.THREADS, params=params)
     return _MEMO[id(pg)]
 
 
@@ -34,22 +34,14 @@ def batches():
     return (("hubs", pg, None), ("wide routers", wpg, wp))
 
 
-def run(pg, params=None):
-    with A.DecompBatch(0, params) as b:
-        b.add(pg); b.upload(); b.run(); b.download()
-        used = {c: b.class_info(c)["n_graphs"] for c in range(K["NUM_CLASSES"]) if b.class_info(c)["n_graphs"]}
-        return b.result(), b.iterations(), used
-
-
 def test_hub_batches_match_oracle():
     """records, statuses (all 0) and iteration counts of both batches"""
     for name, pg, prm in batches():
         want, st, _ = oracle(pg, prm)
-        got, it, _ = run(pg, prm)
-        bad = common.compare_results(want, got, pg.n, conf_tol=1e-9)
-        assert not bad, f"{name}: {len(bad)} mismatches, first {bad[:3]}"
-        assert int((got.status != 0).sum()) == 0, name
-        assert np.array_equal(it, st[:, 3]), (name, np.nonzero(it != st[:, 3])[0][:10])
+        r = DR.run(pg, prm)
+        bad = DR.oracle_mismatches(name, r, want, st[:, 3])
+        assert not bad, f"{len(bad)} mismatches, first {bad[:3]}"
+        assert int((r.result.status != 0).sum()) == 0, name
 
 
 def test_hubs_with_a_zero_count_edge_on_gpu():
@@ -58,15 +50,11 @@ def test_hubs_with_a_zero_count_edge_on_gpu():
     router that fired on the hub before it, with its vertex, type and leftover ratio."""
     pg, _ = shapes.zero_count_batch()
     want, _, _ = oracle(pg)
-    traces = common.oracle_run(pg, threads=THREADS, trace=True)[3]
-    with A.DecompBatch(0, None, trace_events=4096) as b:
-        b.add(pg); b.upload(); b.run(); b.download()
-        got = b.result()
-        assert not common.compare_results(want, got, pg.n, conf_tol=1e-9)
-        assert (got.status >= 100).all()
-        for g in range(pg.n):
-            mine = [(c, a, bb, v) for c, a, bb, v in b.trace(g)]
-            assert mine == traces[g], f"graph {g} diverges from the oracle's op trace"
+    traces = common.oracle_run(pg, threads=DR.THREADS, trace=True)[3]
+    r = DR.run(pg, trace_cap=4096)
+    bad = DR.oracle_mismatches("zero counts", r, want, None, traces)
+    assert not bad, f"{len(bad)} mismatches, first {bad[:3]}"
+    assert (r.result.status >= 100).all()
     assert sum(1 for t in traces if any(ev[0] in (7, 8) for ev in t)) >= 10            # a router did fire before the assert (OP_UNSPLIT_NOW / _BEST)
 
 
@@ -90,12 +78,9 @@ def test_op_trace_of_the_hubs_on_gpu():
         idx, have = trace_subset(pg, per_graph, st[:, 3], cap - 64)
         seen |= have
         sub = pg.select(idx)
-        traces = common.oracle_run(sub, threads=THREADS, trace=True, params=prm)[3]
-        with A.DecompBatch(0, prm, trace_events=cap) as b:
-            b.add(sub); b.upload(); b.run(); b.download()
-            for g in range(sub.n):
-                mine = [(c, a, bb, v) for c, a, bb, v in b.trace(g)]
-                assert mine == traces[g], f"{name}: graph {int(idx[g])} diverges from the oracle's op trace at {next((i for i, (x, y) in enumerate(zip(mine, traces[g])) if x != y), min(len(mine), len(traces[g])))}"
+        want, st, _, traces = common.oracle_run(sub, threads=DR.THREADS, trace=True, params=prm)
+        bad = DR.oracle_mismatches(name, DR.run(sub, prm, trace_cap=cap), want, st[:, 3], dict(zip(idx.tolist(), traces)), traced=idx)
+        assert not bad, f"{len(bad)} mismatches, first {bad[:3]}"
     fans = {(fb, d) for fb in shapes.fan_buckets(K) for d in (0, 1)} - {("1", 1)}
     assert fans <= {(x[1], x[2]) for x in seen if x[0] == "fan"}
     # every router bucket of the census; the zero-count one lives in the batch test_hubs_with_a_zero_count_edge_on_gpu traces whole
@@ -109,25 +94,22 @@ def test_graphs_of_twin_size_on_the_twins_and_off(monkeypatch):
     _, _, cl = common.emu_run(pg)
     idx = np.nonzero(np.isin(cl, list(K["TWINS"])))[0]
     assert idx.size >= 20
-    sub = pg.select(idx); want = common.oracle_run(sub, threads=THREADS)[0]
+    sub = pg.select(idx); want = common.oracle_run(sub, threads=DR.THREADS)[0]
     for force in ("1", "0"):
         monkeypatch.setenv("ALD_DEBUG_TWIN", force)
-        got, _, used = run(sub)
-        assert not common.compare_results(want, got, sub.n, conf_tol=1e-9), force
-        assert (got.status == 0).all()
-        assert set(used) <= (set(K["TWINS"].values()) | {9} if force == "1" else set(K["TWINS"]) | {9}), (force, used)
+        r = DR.run(sub)
+        assert not DR.oracle_mismatches("twins " + force, r, want, want_classes=(set(K["TWINS"].values()) if force == "1" else set(K["TWINS"])) | {9})
+        assert (r.result.status == 0).all()
 
 
-def test_hub_batches_started_one_class_too_low(monkeypatch):
+def test_hub_batches_started_one_class_too_low():
     """ALD_DEBUG_UNDERCLASS=1: the wide hubs outgrow the class they start in and are re-queued one class up"""
     for name, pg, prm in batches():
         want, _, _ = oracle(pg, prm)
-        _, _, plain = run(pg, prm)
-        monkeypatch.setenv("ALD_DEBUG_UNDERCLASS", "1")
-        got, _, used = run(pg, prm)
-        monkeypatch.delenv("ALD_DEBUG_UNDERCLASS")
-        assert not common.compare_results(want, got, pg.n, conf_tol=1e-9), name
-        assert (got.status == 0).all(), name
+        plain = DR.run(pg, prm).classes
+        r = DR.run(pg, prm, env={"ALD_DEBUG_UNDERCLASS": "1"}); used = r.classes
+        assert not DR.oracle_mismatches(name, r, want), name
+        assert (r.result.status == 0).all(), name
         lowered = {}
         for c, k in plain.items(): lowered[max(c - 1, 0)] = lowered.get(max(c - 1, 0), 0) + k
         print(name, "classes: plain", plain, "started one lower", lowered, "ended in", used)
@@ -151,21 +133,16 @@ def test_raw_hub_graphs_through_the_device_pre_steps():
     """hub graphs handed over raw (add_raw, phases as exon-coordinate lists): the wave that loads a graph folds the boundary edges at the source
     and the sink -- where hubs live -- before it decomposes it; against the oracle's pre-steps + decomposition"""
     import test_hub_shapes_cpu as T
-    import test_pre_steps_cpu as P
     from aletsch_amd.packed import PackedGraphs
     O = common.oracle_lib()
     O.ora_pre_assemble.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_void_p)]
     O.ora_staged_view.argtypes = [C.c_void_p, C.c_void_p]; O.ora_staged_free.argtypes = [C.c_void_p]; O.ora_staged_boundary_maps.argtypes = [C.c_void_p] * 5
     items, staged, ok = T.raw_items(O, stride=3)
     ok = np.array(ok)
-    with A.DecompBatch(0) as b:
-        for pg, phases, dist in items:
-            assert b.add_raw(pg, phases, dist) == 0
-        b.upload(); b.run(); b.download()
-        got = b.result()
+    got = DR.run(items, raw=True).result
     assert len(items) > 300 and ok.sum() >= 0.9 * len(ok)
-    want = common.oracle_run(PackedGraphs.concat(staged), threads=THREADS)[0]
-    assert not common.compare_results(want, P.common_select_results(got, np.nonzero(ok)[0]), len(staged), conf_tol=1e-9)
+    want = common.oracle_run(PackedGraphs.concat(staged), threads=DR.THREADS)[0]
+    assert not common.compare_results(want, common.select_results(got, np.nonzero(ok)[0]), len(staged), conf_tol=1e-9)
     assert (got.status[~ok] >= 100).all()
     emu, _ = common.emu_run_raw(items)
     assert not common.compare_results(emu, got, len(items), conf_tol=1e-9)

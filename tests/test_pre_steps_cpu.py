@@ -88,13 +88,10 @@ def test_pre_steps_in_the_load_phase_of_the_engine():
     want, st, _, _ = common.oracle_run(batch)
     ok = ~asserted
     # compare graph by graph: the emulated batch holds the asserted graphs too
-    sub = common_select_results(got, np.nonzero(ok)[0])
+    sub = common.select_results(got, np.nonzero(ok)[0])
     assert not common.compare_results(want, sub, batch.n)
     good = want.status == 0
     assert np.array_equal(it[ok][good], st[good, 3]) and good.sum() > 150
-
-
-common_select_results = common.select_results          # (the helper lives in common.py; the name stays for the modules that import it from here)
 
 
 def test_pre_steps_by_hand():

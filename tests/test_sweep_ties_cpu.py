@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 import common
+import device_run as DR
 import sweep_cases as SC
 
 # the emulation legs: (force_class, kept-records build)
@@ -52,6 +53,6 @@ def test_emulation_matches_oracle(leg):
         assert np.array_equal(it[good], o["iters"][good]), (leg, name, np.nonzero(it != o["iters"])[0][:10])
         for g in np.nonzero(good)[0]:
             a, b = traces[g], o["traces"][g]
-            assert a == b, f"{leg}, {name}, graph {g} ({o['labels'][g] if o['labels'] else ''}): first divergence at {next((i for i, (x, y) in enumerate(zip(a, b)) if x != y), min(len(a), len(b)))}"
+            assert a == b, f"{leg}, {name}, graph {g} ({o['labels'][g] if o['labels'] else ''}): first divergence at {DR.first_divergence(a, b)}"
         n += pg.n
     print(f"{leg}: {n} graphs, 0 mismatches")

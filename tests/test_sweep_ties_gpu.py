@@ -20,11 +20,14 @@ import time
 import numpy as np
 import pytest
 
+import class_cases as CC
 import common
+import device_run as DR
 import sweep_cases as SC
-from test_class_matrix_gpu import KERNELS, IDS, _env
 
 pytestmark = pytest.mark.gpu
+
+KERNELS, IDS = DR.forced_kernels(CC.CLASSES, twins=(11, 12))
 
 
 def test_census_of_the_cases_on_this_machine():
@@ -36,8 +39,8 @@ def test_census_of_the_cases_on_this_machine():
 
 
 @pytest.mark.parametrize("first,twin,cls", KERNELS, ids=IDS)
-def test_plain_kernel_matches_oracle(monkeypatch, first, twin, cls):
-    _env(monkeypatch, first, twin); t0 = time.perf_counter(); n = 0
+def test_plain_kernel_matches_oracle(first, twin, cls):
+    t0 = time.perf_counter(); n = 0
     for name, o in SC.runs().items():
         bad = SC.device_mismatches(name, first, cls)
         assert not bad, f"class {cls}: {len(bad)} mismatches, first {bad[:3]}"

@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 
 import common
+import device_run as DR
 import turn_handover_cases as T
 from aletsch_amd.packed import export_via
 
@@ -40,7 +41,7 @@ def check(name, pg, o, params=None, force_class=0, keep=False, cap=T.TRACE_CAP):
     assert np.array_equal(it, o["iters"]), (name, force_class, keep, np.nonzero(it != o["iters"])[0][:10])
     for g in range(pg.n):
         a, b = mine[g], o["traces"][g]
-        assert a == b, f"{name}, class >= {force_class}, keep {keep}, graph {g}: first divergence at {next((i for i, (x, y) in enumerate(zip(a, b)) if x != y), min(len(a), len(b)))}"
+        assert a == b, f"{name}, class >= {force_class}, keep {keep}, graph {g}: first divergence at {DR.first_divergence(a, b)}"
     return cl
 
 

@@ -16,13 +16,13 @@ import turn_handover_cases as T
 pytestmark = pytest.mark.gpu
 
 
-@pytest.mark.parametrize("first,twin", T.FORCINGS, ids=["class0", "class1", "class2", "twin11"])
-def test_batches_match_oracle(first, twin):
+@pytest.mark.parametrize("first,twin,cls", T.FORCINGS, ids=["class0", "class1", "class2", "twin11"])
+def test_batches_match_oracle(first, twin, cls):
     """(the `dominate_flip` case of batch 4 is live HERE: with 64 lanes the dominate queries of its first scan are answered within the first
     chunk, the scan starts again at vertex 1, counts one candidate and the flag is cleared before the star -- only the refreshed phasing
     flags bring it back for the vertex that star turns into a type-1 one)"""
     for name, pg, prm in T.gpu_batches():
-        bad = T.device_mismatches(name, pg, T.oracle(name, pg, prm), prm, first, twin)
+        bad = T.mismatches_on_device(name, pg, T.oracle(name, pg, prm), prm, first, twin, cls)
         assert not bad, bad[:3]
 
 
@@ -30,8 +30,8 @@ def test_raw_form_of_the_bench_batch():
     """add_packed_raw: the pre-steps run in the load phase of the raw build of the kernel, then the same sweeps"""
     items, raw_pg, staged = T.bench_raw()
     o = T.oracle("bench_raw", staged)
-    for first, twin in T.FORCINGS[:3]:
-        bad = T.device_mismatches("bench", raw_pg, o, None, first, twin, raw=True)
+    for first, twin, cls in T.FORCINGS[:3]:
+        bad = T.mismatches_on_device("bench", raw_pg, o, None, first, twin, cls, raw=True)
         assert not bad, bad[:3]
 
 

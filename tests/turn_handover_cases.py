@@ -9,16 +9,14 @@ The hand-made graphs are layered: the source reaches every vertex of the first l
 connected, every vertex of the last layer reaches the sink by two parallel edges.  Every inner vertex then has two or more edges on both
 sides, no vertex is trivial, and the first rule that fires is the smallest-edge rule on the edge whose weight was made small: which edge was
 removed, where it stood in its two lists and what the degrees were is known from the packed graph and the first trace event alone."""
-import os
-
 import numpy as np
 
 import aletsch_amd as A
 from aletsch_amd.packed import PackedGraphs
 import common
+import device_run as DR
 import shapes
 
-THREADS = max(1, min(16, len(os.sched_getaffinity(0))))
 TRACE_CAP = 1 << 13
 OP_BROKEN, OP_TRIVIAL_FAST, OP_TRIVIAL_NOW, OP_TRIVIAL_BEST, OP_SMALL_NOW, OP_SMALLEST = 1, 2, 3, 4, 5, 6
 _CACHE = {}
@@ -188,7 +186,7 @@ def oracle(key, pg, params=None):
     """records, statistics and op traces of a batch, computed once -> dict(res, iters, traces)"""
     k = "oracle_" + key
     if k not in _CACHE:
-        res, st, _, tr = common.oracle_run(pg, threads=THREADS, trace=True, params=params)
+        res, st, _, tr = common.oracle_run(pg, threads=DR.THREADS, trace=True, params=params)
         _CACHE[k] = dict(res=res, iters=st[:, 3].copy(), traces=tr)
     return _CACHE[k]
 
@@ -224,35 +222,12 @@ def bench_raw(stride=3):
     return _CACHE["raw"]
 
 
-# (first class, ALD_DEBUG_TWIN): the one-chunk, two-chunk and many-chunk forms of the sweeps and the slab form (7 with the twins on: class 11)
-FORCINGS = ((0, "0"), (1, "0"), (2, "0"), (7, "1"))
+# (first class, ALD_DEBUG_TWIN, class): the one-chunk, two-chunk and many-chunk forms of the sweeps and the slab form (7 with the twins on: class 11)
+FORCINGS = tuple(DR.forced_kernels((0, 1, 2), twins=(11,))[0])
 
 
-def run_on_device(pg, params=None, first=0, twin="0", raw=False):
-    """the batch through the library the process has loaded, every graph traced -> (DecompResult, iterations, classes used, traces)"""
-    os.environ["ALD_DEBUG_FIRST_CLASS"] = str(first); os.environ["ALD_DEBUG_TWIN"] = twin
-    try:
-        with A.DecompBatch(0, params, trace_events=TRACE_CAP) as b:
-            if raw: b.add_packed_raw(pg, 10000)
-            else: b.add(pg)
-            b.upload(); b.run(); b.download()
-            used = {c for c in range(14) if b.class_info(c)["n_graphs"]}
-            return b.result(), b.iterations(), used, [[(c, a, bb, v) for c, a, bb, v in b.trace(g)] for g in range(pg.n)]
-    finally:
-        del os.environ["ALD_DEBUG_FIRST_CLASS"], os.environ["ALD_DEBUG_TWIN"]
-
-
-def device_mismatches(name, pg, o, params=None, first=0, twin="0", raw=False):
-    """-> list of differences between the device and the oracle (records with conf within 1e-9 as in the whole GPU tier, everything else exact;
-    statuses, iteration counts, op traces)"""
-    got, it, used, traces = run_on_device(pg, params, first, twin, raw)
+def mismatches_on_device(name, pg, o, params=None, first=0, twin="0", cls=0, raw=False):
+    """the batch with the first class forced, every graph traced, against its cached oracle answer (no graph below the forced class)"""
+    r = DR.run(pg, params, first=first, twin=twin, raw=raw, trace_cap=TRACE_CAP)
     tag = f"{name}, first class {first}, twin {twin}" + (", raw" if raw else "")
-    bad = [(tag,) + tuple(x) for x in common.compare_results(o["res"], got, pg.n, conf_tol=1e-9)]
-    if not np.array_equal(got.status, o["res"].status): bad.append((tag, "status"))
-    if not np.array_equal(it, o["iters"]): bad.append((tag, "iterations", np.nonzero(it != o["iters"])[0][:5].tolist()))
-    want_cls = 11 if twin == "1" else first
-    if not used <= {c for c in range(want_cls, 14)} - ({7} if twin == "1" else set()): bad.append((tag, "classes", sorted(used)))
-    for g in range(pg.n):
-        if traces[g] != o["traces"][g]:
-            bad.append((tag, "trace of graph %d" % g, next((i for i, (x, y) in enumerate(zip(traces[g], o["traces"][g])) if x != y), -1))); break
-    return bad
+    return DR.oracle_mismatches(tag, r, o["res"], o["iters"], o["traces"], want_classes=set(range(cls, DR.N_CLASSES)))

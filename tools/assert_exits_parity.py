@@ -7,13 +7,14 @@ from parity_runner import run_libraries
 CHILD = r'''
 import assert_cases as AC
 tot = 0; nbad = 0
-for first, twin in ((0, "0"), (1, "0"), (2, "0"), (7, "1")):
+for first, twin, _ in DR.forced_kernels((0, 1, 2), twins=(11,))[0]:
     n, bad = AC.site_mismatches_on_device(first, twin)
     tot += n; nbad += len(bad)
     if bad: print("   mismatch", bad[:3], flush=True)
 o = AC.successor_batch()
-got, used, mine = AC.run_on_device(o["pg"], o["params"], AC.SUCCESSOR_CLASS)
-bad = AC.device_mismatches("interleaved", got, mine, o["want"], o["traces"])
+assert max(len(t) for t in o["traces"]) < AC.TRACE_CAP
+r = DR.run(o["pg"], o["params"], first=AC.SUCCESSOR_CLASS, trace_cap=AC.TRACE_CAP)
+bad = DR.oracle_mismatches("interleaved", r, o["want"], None, o["traces"])
 tot += o["pg"].n; nbad += len(bad)
 if bad: print("   mismatch", bad[:3], flush=True)
 print("   TOTAL graphs", tot, "mismatches", nbad, flush=True)

@@ -9,7 +9,6 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, 'tests'))
 import aletsch_amd as A, common
 from aletsch_amd.packed import PackedGraphs
-import test_pre_steps_cpu as T
 O = common.oracle_lib()
 O.ora_pre_assemble.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_void_p)]
 O.ora_staged_view.argtypes = [C.c_void_p, C.c_void_p]; O.ora_staged_free.argtypes = [C.c_void_p]; O.ora_staged_boundary_maps.argtypes = [C.c_void_p] * 5
@@ -44,7 +43,7 @@ while time.time() < t_end:
     if want_parts:
         batch = PackedGraphs.concat(want_parts)
         want = common.oracle_run(batch, threads=8)[0]
-        sub = T.common_select_results(got, np.nonzero(~asserted)[0])
+        sub = common.select_results(got, np.nonzero(~asserted)[0])
         bad += common.compare_results(want, sub, batch.n, conf_tol=1e-9)
     ntot += n; nbad += len(bad); nassert += int(asserted.sum())
     print(k, "graphs", n, "dist", dist, "big" if big else "small", "asserted", int(asserted.sum()), "MISMATCH " + str(bad[:3]) if bad else "ok", flush=True)

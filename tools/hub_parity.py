@@ -9,8 +9,8 @@ tot = 0; nbad = 0
 pg, _ = shapes.hub_batch(); wpg, _, wp = shapes.wide_router_batch(); zpg, _ = shapes.zero_count_batch()
 for name, b, prm in (("hubs", pg, None), ("wide routers", wpg, wp), ("zero counts", zpg, None)):
     want = common.oracle_run(b, threads=threads, params=prm)[0]
-    got = A.decompose(b, 0, prm)
-    bad = common.compare_results(want, got, b.n, conf_tol=1e-9)
+    r = DR.run(b, prm); got = r.result
+    bad = DR.oracle_mismatches(name, r, want)
     tot += b.n; nbad += len(bad)
     print("   batch", name, "graphs", b.n, "mismatch", bad[:3], "status", dict(zip(*[a.tolist() for a in np.unique(got.status, return_counts=True)])), flush=True)
 print("   TOTAL graphs", tot, "mismatches", nbad, flush=True)

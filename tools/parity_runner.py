@@ -6,8 +6,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PRELUDE = r'''
 import sys, os, numpy as np
 sys.path.insert(0, %r); sys.path.insert(0, os.path.join(%r, "tests"))
-import aletsch_amd as A, common
-threads = max(1, min(16, len(os.sched_getaffinity(0))))
+import aletsch_amd as A, common, device_run as DR
+threads = DR.THREADS
 ''' % (ROOT, ROOT)
 
 

@@ -5,7 +5,6 @@ import sys
 from parity_runner import run_libraries
 CHILD = r'''
 import sweep_cases as SC
-os.environ["ALD_DEBUG_FIRST_CLASS"] = "0"; os.environ["ALD_DEBUG_TWIN"] = "0"
 tot = 0; nbad = 0
 for name, o in SC.runs().items():
     bad = SC.device_mismatches(name)

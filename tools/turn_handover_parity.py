@@ -9,8 +9,8 @@ import turn_handover_cases as T
 tot = 0; nbad = 0
 for name, pg, prm in T.gpu_batches():
     o = T.oracle(name, pg, prm)
-    for first, twin in T.FORCINGS:
-        bad = T.device_mismatches(name, pg, o, prm, first, twin)
+    for first, twin, cls in T.FORCINGS:
+        bad = T.mismatches_on_device(name, pg, o, prm, first, twin, cls)
         tot += pg.n; nbad += len(bad)
         if bad: print("   mismatch", bad[:3], flush=True)
 print("   TOTAL graphs", tot, "mismatches", nbad, flush=True)

@@ -8,10 +8,8 @@ tot = 0; nbad = 0; ntwin = 0
 for seed, epv in ((11, 3), (12, 3), (13, 4), (14, 2)):
     pg = A.synth(seed=seed, n_graphs=50, v_min=385, v_max=512, edges_per_vertex=epv)
     want = common.oracle_run(pg, threads=threads)[0]
-    with A.DecompBatch(0) as b:
-        b.add(pg); b.upload(); b.run(); b.download(); got = b.result()
-        info = {c: b.class_info(c)["n_graphs"] for c in range(14) if b.class_info(c)["n_graphs"]}
-    bad = common.compare_results(want, got, pg.n, conf_tol=1e-9)
+    r = DR.run(pg); got = r.result; info = r.classes
+    bad = DR.oracle_mismatches("seed %d" % seed, r, want)
     tot += pg.n; nbad += len(bad); ntwin += info.get(11, 0) + info.get(12, 0)
     print("   seed", seed, "classes", info, "mismatch", len(bad), "status", dict(zip(*[a.tolist() for a in np.unique(got.status, return_counts=True)])), flush=True)
 print("   TOTAL graphs", tot, "on the twins", ntwin, "mismatches", nbad, flush=True)
